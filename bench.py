@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Bench: structures/sec (graph + Betti) on synthetic crystal batches, 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--structures B] [...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--structures B] [--dump-outputs DIR] [--full] [...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line; the legs that take runs of
+their own (`roofline.rbf_*`, `side`, `cpu_baseline` / `parity`) are measured only with --full.
+--dump-outputs DIR writes what the last timed step left in the shard's output buffers as
+DIR/<name>.npy (f64; rbf.npy f32 for an f32 RBF) for a fixed, seeded sample of the shard's atoms and
+their edges (see dump_outputs); the synthetic inputs depend on the arguments alone, so two builds
+can be compared array for array.
 
 Workload (BASELINE.json configs[3], one shard per GPU, weak scaling): every rank owns B = 8,192
 jittered 256-atom FCC structures (structure ids [rank*B, (rank+1)*B)), inputs resident in HBM.
@@ -17,7 +24,8 @@ and the max-over-ranks of the timed region.
 Rank 0 prints ONE JSON line (metric/unit from BASELINE.json) with
   roofline      the neighbour + RBF path (prep + count + scan + emit, HBM-bound) at SURVEY 8(d)'s
                 algorithmic bytes over its HIP-event time on the launch stream; the emit launch
-                alone and the f32-RBF variant (measured after the timed loop) beside it
+                alone beside it, and with --full the f32-RBF variant (measured after the timed loop)
+and, with --full only,
   side          beside the headline, never part of `value`: BASELINE configs 1, 2, 3 and 5 (the
                 741.vasp POSCAR through the reference CPU path and the GPU path; 1,024 x SC-64 graph
                 / graph + Betti; one 4,096-atom supercell) and the Betti pass at the reference's
@@ -59,6 +67,11 @@ def parse():
     ap.add_argument("--no-betti", action="store_true", help="graph only (config 2 style)")
     ap.add_argument("--rbf-dtype", default="f64", choices=["f64", "f32"],
                     help="edge_attr dtype of the timed step (the reference's is f64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the other-RBF-dtype path, the side lines and "
+                         "the CPU baseline with its parity check (each has a --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="directory: after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-alt-rbf", action="store_true", help="skip the other-RBF-dtype side measurement")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the timing barrier / max (nccl = RCCL)")
@@ -73,7 +86,10 @@ def parse():
     ap.add_argument("--config", default=None, help="label of the BASELINE config this run measures")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per neighbour-path launch set (profiles/collect.sh)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def graph_bytes_8d(n_atoms, n_struct, edges, nbins, rbf_bytes):
@@ -158,6 +174,8 @@ def main():
         bad = int(torch.isnan(sh.out["feat"]).any(dim=1).sum().item())
         if bad:
             raise SystemExit(f"rank {rank}: {bad} atoms with NaN features")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sh, torch)
 
     total_structures = B * world * args.steps
     value = total_structures / elapsed
@@ -188,7 +206,7 @@ def main():
                 "emit_only": {"avg_launch_ms": round(emit_ms, 4),
                               "achieved": round(algo / (emit_ms * 1e-3) / 1e9, 1),
                               "frac": round(algo / (emit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
-        if not args.no_alt_rbf:
+        if args.full and not args.no_alt_rbf:
             alt = "f32" if f64 else "f64"
             roof["rbf_" + alt] = alt_rbf_measurement(ctx, sh, args, nbins, abi, dgn, torch, alt)
     dk = ktimes.get("betti_dist", {})
@@ -221,9 +239,9 @@ def main():
     }
     if args.dump_shards:
         dump_shard(args.dump_shards, rank, sh, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = cpu_baseline(args, sh, n_atoms, torch)
-    if not args.no_side and world == 1:
+    if args.full and not args.no_side and world == 1:
         result["side"] = side_lines(dgn, abi, ctx, dev, args, torch)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -239,6 +257,38 @@ def dump_shard(d, rank, sh, args):
     for k in ("row_ptr", "col", "dist", "feat", "counts"):
         if k in sh.out:
             np.save(os.path.join(d, f"rank{rank}_{k}.npy"), sh.out[k].cpu().numpy())
+
+
+DUMP_ATOMS = 32768          # sampled atoms: feat 9.2 MB, counts 1 MB, row_ptr + atom ids 0.5 MB
+DUMP_EDGES = 786432         # their edges, truncated: col + dist + edge ids 18.9 MB
+DUMP_RBF_BYTES = 24 << 20   # RBF rows of the first of those edges (54 MB in all at most, under the 64 MB cap)
+
+
+def dump_outputs(d, sh, torch):
+    """--dump-outputs: what the last timed step left in the shard's output buffers (the arrays
+    dgn_dev_graph_betti hands its caller), as DIR/<name>.npy. The full shard is gigabytes, so a fixed
+    sample: DUMP_ATOMS atoms drawn without replacement by numpy's default_rng(0x5EED), sorted
+    (atoms.npy), with feat / counts / row_ptr (the start of each atom's row) for them; the edges of
+    those atoms in CSR order, the first DUMP_EDGES at most (edges.npy), with col / dist; and rbf for
+    the first of those edges that fit DUMP_RBF_BYTES. Everything f64, rbf in the timed step's dtype."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    o, dev = sh.out, sh.dev
+    atoms_h = np.sort(np.random.default_rng(0x5EED).choice(sh.A, size=min(sh.A, DUMP_ATOMS), replace=False))
+    atoms = torch.from_numpy(atoms_h).to(dev)
+    start, end = o["row_ptr"][atoms], o["row_ptr"][atoms + 1]
+    deg = end - start
+    first = torch.cumsum(deg, 0) - deg  # position of each atom's first edge in the sample
+    n_e = int(deg.sum().item())
+    edges = (torch.repeat_interleave(start - first, deg) + torch.arange(n_e, device=dev))[:DUMP_EDGES]
+    arrays = {"atoms": atoms.double(), "row_ptr": start.double(), "edges": edges.double(),
+              "col": o["col"][edges].double(), "dist": o["dist"][edges]}
+    rbf = o["rbf"]
+    arrays["rbf"] = rbf[edges[:DUMP_RBF_BYTES // (rbf.shape[1] * rbf.element_size())]]
+    if "feat" in o:
+        arrays.update(feat=o["feat"][atoms], counts=o["counts"][atoms].double())
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v.cpu().numpy())
 
 
 def alt_rbf_measurement(ctx, sh, args, nbins, abi, dgn, torch, alt):

@@ -12,7 +12,7 @@ set -eo pipefail
 OUT=${1:-gpurun_out/prof_r05}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-side"
+BENCH="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-side"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 $BENCH > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err"; echo "1 trace ok"
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- \

@@ -61,7 +61,7 @@ def test_bench_one_rank_nccl(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--structures", str(B), "--steps", "2", "--warmup", "1", "--no-side", "--no-cpu-baseline",
-           "--no-alt-rbf", "--dump-shards", str(tmp_path)]
+           "--no-alt-rbf", "--dump-shards", str(tmp_path), "--dump-outputs", str(tmp_path / "out")]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -69,4 +69,20 @@ def test_bench_one_rank_nccl(tmp_path):
     assert len(lines) == 1, r.stdout[-2000:]
     j = json.loads(lines[0])
     assert j["n_gpus"] == 1 and j["value"] > 0 and j["config"]["structures_per_gpu"] == B
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    # a plain run measures nothing beside the timed steps
+    assert "side" not in j and "cpu_baseline" not in j and "rbf_f32" not in (j["roofline"] or {})
     assert (tmp_path / "rank0_counts.npy").exists()
+    # --dump-outputs: a sample of the same buffers, f32/f64 .npy, 64 MB at most
+    out = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(out) == {"atoms", "row_ptr", "edges", "col", "dist", "rbf", "feat", "counts"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    atoms, edges = out["atoms"].astype(np.int64), out["edges"].astype(np.int64)
+    assert len(atoms) == B * 256 and np.array_equal(atoms, np.arange(B * 256))  # the whole small shard
+    full = {k: np.load(tmp_path / f"rank0_{k}.npy") for k in ("row_ptr", "col", "dist", "feat", "counts")}
+    assert np.array_equal(out["row_ptr"], full["row_ptr"][atoms])
+    assert len(edges) and np.array_equal(edges, np.arange(full["row_ptr"][-1])[:len(edges)])
+    assert np.array_equal(out["col"], full["col"][edges]) and np.array_equal(out["dist"], full["dist"][edges])
+    assert np.array_equal(out["feat"], full["feat"][atoms]) and np.array_equal(out["counts"], full["counts"][atoms])
+    assert out["rbf"].shape[1] == 50 and 0 < len(out["rbf"]) <= len(edges)
