@@ -333,7 +333,8 @@ struct Complex {
     // F-minimal cofacet (recorded for every column by the lane-parallel pass; tree edges and
     // cleared triangles hold kNone), else kNone.
     __device__ uint32_t apparent_owner_wave(int dim, uint64_t tau) const {
-        // computed redundantly by every lane on the VALU (the scalar unit is the bound port)
+        // computed redundantly by every lane on the VALU (the scalar unit is the bound port; the
+        // earlier form ran max_facet on the uniform tau)
         uint32_t th, tl;
         asm("v_mov_b32 %0, %1" : "=v"(th) : "s"((uint32_t)(tau >> 32)));
         asm("v_mov_b32 %0, %1" : "=v"(tl) : "s"((uint32_t)tau));
@@ -342,9 +343,6 @@ struct Complex {
         const uint32_t vm = at(mincof_of(dim), dim == 1 ? col_dense(1, vf)
                                                          : tri_dense_lane((vf >> 16) & 255, (vf >> 8) & 255, vf & 255));
         return uni(vm == extra_vertex(key_packed(vt), vf) ? vf : kNone);
-        const uint32_t f = uni(max_facet(dim, uni64(tau)));
-        const uint32_t m = at(mincof_of(dim), col_dense(dim, f));
-        return uni(m) == extra_vertex(key_packed(tau), f) ? f : kNone;
     }
 
     __device__ uint64_t column_key(int dim, uint32_t cp) const {

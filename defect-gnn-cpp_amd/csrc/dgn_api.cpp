@@ -153,6 +153,7 @@ struct dgn_ctx {
     hipEvent_t ev_walk[2] = {nullptr, nullptr}, ev_red[2] = {nullptr, nullptr};
     bool dbg_wide_walk = true;     // the u16-coded complexes' dim-2 walk as a workgroup-per-complex pass
     int dbg_split_chunk = 0;       // clouds per chunk of the component split (0 = its byte budget)
+    int dbg_walk_slice = 0;        // complexes per slice of the u16-coded wide list (0 = its byte budgets)
     int dbg_big_log2 = 0;          // capacity-retry layout's first-level table size log2 (0 = natural 24)
     int dbg_emit_chunk = 0;        // tiles per launch of the large-row emit (0 = the byte budget's)
     // host staging
@@ -336,7 +337,6 @@ int graph_count_impl(dgn_ctx* c, const dgn_batch* b, double rc, uint64_t kmax, d
     // the Betti weights ride along with any pass that has species, so a Betti pass at the same
     // cutoff can reuse this one (betti_impl)
     const bool want_weight = b->species != nullptr;
-    (void)betti;
     if (want_weight) HIP_TRY(c, W.weight.ensure(sizeof(double) * A1));
     HIP_TRY(c, c->scalars.ensure(sizeof(Scalars)));
     Scalars* sc = c->scalars.as<Scalars>();
@@ -435,35 +435,74 @@ int check_emit_flag(dgn_ctx* c) {
     return take_flags(c);
 }
 
-int betti_impl(dgn_ctx* c, const dgn_batch* b, double rc, double* features, int32_t* counts, const double* clouds,
-               const int32_t* npoints, int32_t cloud_stride, int64_t num_clouds, float* pairs_out, int32_t pair_cap,
-               const float* lower = nullptr, bool reuse_graph = false, bool async_report = false) {
-    const bool given = clouds || lower;
-    const int64_t A = given ? num_clouds : b->num_atoms;
-    auto nw = [&]() -> GraphWork& { return reuse_graph ? c->gw : c->bw; };
-    if (A == 0) return DGN_OK;
-    int max_points = cloud_stride;
-    if (!given) {
-        // NeighborList(rc, SIZE_MAX) counts (betti_features.cpp:107): the largest local complex,
-        // sum n^2 for the byte accounting, the per-atom weights
-        // dgn_dev_graph_betti: the graph pass's count at the same cutoff already holds every
-        // neighbour within rc (NeighborList(rc, K) and NeighborList(rc, SIZE_MAX) see the same
-        // candidates, neighbor_list.cpp:27-66); its per-atom counts, hit masks, cell lists and
-        // weights serve the Betti search unchanged
-        if (!reuse_graph) {
-            int64_t E = 0;
-            int st = graph_count_impl(c, b, rc, UINT64_MAX, 1e-10, &E, true);
-            if (st) return st;
-        }
-        max_points = (int)nw().max_candidates + 1;
-    }
-    // caller-given triangles (one connected component at a time, dgn_host_persistence's split) reach
-    // the GIANT instantiation; clouds and atom-centred complexes stop at the distance kernels' 2,048
-    const int envelope = lower ? kWideGiantPoints : betti_max_points();
-    if (max_points > envelope)
-        return fail(c, DGN_ERR_UNSUPPORTED,
-                    "local complex with " + std::to_string(max_points) + " points exceeds the " +
-                        std::to_string(envelope) + "-point kernel envelope (see DESIGN.md)");
+// ---- the Betti pass's host driver: betti_impl and its steps ----
+
+// floats per complex of an n-point packed f32 lower triangle: a multiple of 4 (16-byte aligned complexes)
+int64_t tri_stride(int64_t n) { return (n * (n - 1) / 2 + 3) / 4 * 4; }
+// u32 per complex of an n-point complex's rank codes (betti_rank_codes), a multiple of 64
+int64_t rank_stride(int64_t n) { return (n * (n - 1) / 2 + 63) / 64 * 64; }
+
+// a rank buffer for `slice` complexes: codes, sorted values (slice * rstride u32 each), temporary space
+struct RankBuf {
+    uint32_t *codes, *sorted;
+    void* tmp;
+};
+RankBuf carve_rank(void* base, int64_t slice, int64_t rstride) {
+    uint32_t* codes = reinterpret_cast<uint32_t*>(base);
+    uint32_t* sorted = codes + slice * rstride;
+    return {codes, sorted, sorted + slice * rstride};
+}
+
+// free HBM of the current device (0 when the query fails)
+int64_t hbm_free() {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    return (int64_t)free_b;
+}
+// The budget rule of the Betti workspaces: 1 / divisor of the HBM that is free or already held by
+// the workspace that asks (288 GB per MI355X), within [floor_bytes, ceil_bytes]. Counting the
+// workspace in the pool keeps its size, hence its layout, the same from one call to the next.
+// A caller's limit on the library's HBM would be applied here.
+int64_t hbm_share(size_t held_bytes, int64_t divisor, int64_t floor_bytes, int64_t ceil_bytes) {
+    return std::min(ceil_bytes, std::max(floor_bytes, (hbm_free() + (int64_t)held_bytes) / divisor));
+}
+
+// what a Betti pass reduces and where its results go; a caller fills the fields it uses
+struct BettiJob {
+    const dgn_batch* batch = nullptr;  // the atom-centred complexes of a batch (rc = the cutoff), or
+    const double* clouds = nullptr;    // caller-given clouds [count][stride][3], or
+    const float* lower = nullptr;      // caller-given packed triangles [count][C(stride, 2)]
+    const int32_t* npoints = nullptr;  // [count] points of each caller-given complex
+    int32_t stride = 0;                // point slots per caller-given complex
+    int64_t count = 0;                 // caller-given complexes
+    double rc = 0;                     // Vietoris-Rips threshold
+    double* features = nullptr;        // [complexes][35], or null
+    int32_t* counts = nullptr;         // [complexes][4], or null
+    float* pairs = nullptr;            // [complexes][3][pair_cap][2], or null
+    int32_t pair_cap = 0;
+    bool reuse_graph = false;   // the graph pass's count (c->gw) serves as the neighbour pass
+    bool async_report = false;  // device entry points: no host wait, flags at the next synchronizing call
+};
+
+// what the steps of one betti_impl call share, built once per call
+struct BettiPass {
+    BettiLaunch bl{};            // launch template: the call's outputs, lists, queues and counters
+    BettiFork fork{};            // the overflow tier's side stream and events
+    Scalars* sc = nullptr;
+    uint32_t* bflags = nullptr;  // the sticky Betti words (kBF*)
+    int max_points = 0;
+    // wide complexes of <= kC16MaxPoints points run on u16 rank codes, and their dim-2 apparent walk
+    // runs as a workgroup-per-complex pass before the per-wave launch (betti_walk_kernel)
+    bool c16 = false, prewalk = false;
+    WideLayout wl{};  // the regular wide layout and its wave count (plan_wide)
+    int wide_waves = 0;
+    int64_t wide_census = 0;  // upper bound of the call's 65..kWideRegular-point complexes
+    bool async_report = false;
+};
+
+// narrow scratch slots and their first-use initialisation, the overflow fork, the flag words, the
+// overflow and dense lists, and the launch template of the call's A complexes
+int betti_prepare(dgn_ctx* c, const BettiJob& job, int64_t A, BettiPass& P) {
     // scratch slots: the main grid's plus kOverflowWaves for the forked overflow tier
     constexpr int kOverflowWaves = 512;
     if (c->betti_slots == 0) c->betti_slots = betti_grid_waves(c->device) + kOverflowWaves;
@@ -472,7 +511,7 @@ int betti_impl(dgn_ctx* c, const dgn_batch* b, double rc, double* features, int3
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
-    const BettiFork fork{c->side, c->ev_fork, c->ev_join, kOverflowWaves};
+    P.fork = BettiFork{c->side, c->ev_fork, c->ev_join, kOverflowWaves};
     const int64_t spw = betti_scratch_bytes_per_wave();
     if (c->b_scratch.bytes < (size_t)spw * c->betti_slots) {
         HIP_TRY(c, c->b_scratch.ensure((size_t)spw * c->betti_slots));
@@ -485,60 +524,20 @@ int betti_impl(dgn_ctx* c, const dgn_batch* b, double rc, double* features, int3
         c->scratch_fresh = false;
     }
     HIP_TRY(c, c->scalars.ensure(sizeof(Scalars)));
-    Scalars* sc = c->scalars.as<Scalars>();
+    Scalars* sc = P.sc = c->scalars.as<Scalars>();
     HIP_TRY(c, hipMemsetAsync(&sc->graph_flag, 0, 5 * sizeof(uint32_t), c->stream));
     if (!c->bflags.p) {
         HIP_TRY(c, c->bflags.ensure(kBFWords * sizeof(uint32_t)));
         HIP_TRY(c, hipMemsetAsync(c->bflags.p, 0, kBFWords * sizeof(uint32_t), c->stream));
     }
-    uint32_t* bflags = c->bflags.as<uint32_t>();
+    P.bflags = c->bflags.as<uint32_t>();
     HIP_TRY(c, c->b_list.ensure(2 * sizeof(int32_t) * (size_t)A));  // overflow list, dense list
-    // complexes above 64 points: the wide kernel, one wave per complex with a per-wave scratch
-    // (distance matrix, min-cofacet tables, sorted columns, pivot hash) sized for max_points
-    WideLayout wl{};
-    int wide_waves = 0;
-    // wide complexes of <= kC16MaxPoints points run on u16 rank codes, and their dim-2 apparent walk
-    // runs as a workgroup-per-complex pass before the per-wave launch (betti_walk_kernel)
-    const bool c16 = c->dbg_wide_c16 && max_points > 64 && max_points <= kC16MaxPoints;
-    const bool prewalk = c16 && c->dbg_wide_walk;
-    if (max_points > 64) {
-        const int wide_nmax = std::min(max_points, kWideRegular);  // larger: the coded retry launch
-        wl = betti_wide_layout(wide_nmax, false, c->dbg_wide_cap, 0, 24, prewalk);
-        // as many waves as the device keeps resident (dynamic LDS sized by
-        // max_points), each with its own scratch, within half of the HBM that is free or already
-        // this workspace's (288 GB per MI355X; at least 8 GB) -- counting the workspace in the pool
-        // keeps the wave count, hence the layout, the same from one call to the next (a changed
-        // layout re-initialises every wave's tables)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        const int64_t budget =
-            std::max<int64_t>(int64_t(8) << 30, ((int64_t)free_b + (int64_t)c->b_wide.bytes) / 2);
-        const int64_t resident = betti_wide_resident_waves(c->device, wide_nmax, c16, prewalk);
-        wide_waves = (int)std::max<int64_t>(1, std::min<int64_t>({budget / wl.total, resident, A}));
-        if (c->dbg_wide_waves > 0 && c->dbg_wide_waves < wide_waves) wide_waves = c->dbg_wide_waves;  // A/B only
-        const size_t want = (size_t)wl.total * (size_t)wide_waves;
-        const bool grown = c->b_wide.bytes < want;
-        if (grown) HIP_TRY(c, c->b_wide.ensure(want));
-        wl.base = c->b_wide.as<uint8_t>();
-        if (grown || c->wide_nmax != wide_nmax || c->wide_waves != wide_waves || c->wide_cap != wl.na_cap ||
-            c->wide_pre != (int)prewalk) {
-            // the layout depends on max_points: every wave's pivot hash table starts empty (key 0)
-            // and its u16 min-cofacet tables "no cofacet" (0xFFFF); afterwards each reduction
-            // restores both for the entries it used
-            HIP_TRY(c, betti_wide_init_scratch(c->stream, wl, wide_waves));
-            c->wide_nmax = wide_nmax;
-            c->wide_waves = wide_waves;
-            c->wide_cap = wl.na_cap;
-            c->wide_pre = (int)prewalk;
-        }
-        HIP_TRY(c, c->b_wlist.ensure(sizeof(int32_t) * (size_t)A));
-    }
-    BettiLaunch bl{};
+    BettiLaunch& bl = P.bl;
     bl.num_atoms = A;
-    bl.thr = (float)rc;  // ripser_wrapper.cpp:28
-    bl.features = features;
-    bl.counts = counts;
-    bl.error_flag = bflags + kBFReduce;
+    bl.thr = (float)job.rc;  // ripser_wrapper.cpp:28
+    bl.features = job.features;
+    bl.counts = job.counts;
+    bl.error_flag = P.bflags + kBFReduce;
     bl.work_counter = &sc->work_counter;
     bl.work_counter2 = &sc->work_counter2;
     bl.overflow_list = c->b_list.as<int32_t>();
@@ -548,313 +547,426 @@ int betti_impl(dgn_ctx* c, const dgn_batch* b, double rc, double* features, int3
     bl.dense_queue = &sc->dense_queue;
     bl.scratch = c->b_scratch.as<uint8_t>();
     bl.scratch_per_wave = spw;
-    bl.clouds = clouds;
-    bl.npoints = npoints;
-    bl.cloud_stride = cloud_stride;
-    bl.pairs_out = pairs_out;
-    bl.pair_cap = pair_cap;
-    bl.wide_list = max_points > 64 ? c->b_wlist.as<int32_t>() : nullptr;
-    bl.wide_len = &sc->wide_len;
+    bl.clouds = job.clouds;
+    bl.npoints = job.npoints;
+    bl.cloud_stride = job.stride;
+    bl.pairs_out = job.pairs;
+    bl.pair_cap = job.pair_cap;
+    bl.wide_len = &sc->wide_len;  // wide_list: plan_wide
     bl.wide_queue = &sc->wide_queue;
-    HIP_TRY(c, c->b_rlist.ensure(sizeof(int32_t) * (size_t)A));
-    bl.retry_list = c->b_rlist.as<int32_t>();
-    bl.retry_len = &sc->retry_len;
+    bl.retry_len = &sc->retry_len;  // retry_list: betti_impl
     bl.force_retry = c->dbg_force_retry ? 1 : 0;  // tests only (dgn_ctx_set_debug)
-    // Betti pass over complexes [c0, c0 + cnt) whose triangles are in `lower`
-    auto vr_pass = [&](int64_t c0, int64_t cnt, const float* tri, int64_t tri_stride, const int32_t* np,
-                       const double* w, double bytes) -> int {
-        BettiLaunch pb = bl;
-        pb.lower = tri;
-        pb.npoints = np;
-        pb.weight = w;
-        pb.tri_stride = tri_stride;
-        pb.num_atoms = cnt;
-        pb.features = features ? features + 35 * c0 : nullptr;
-        pb.counts = counts ? counts + 4 * c0 : nullptr;
-        pb.pairs_out = pairs_out ? pairs_out + c0 * 3 * (int64_t)pair_cap * 2 : nullptr;
-        static_assert(offsetof(Scalars, dense_queue) - offsetof(Scalars, work_counter) == 8 * sizeof(uint32_t),
-                      "queue and list counters are contiguous");
-        HIP_TRY(c, hipMemsetAsync(&sc->work_counter, 0, 9 * sizeof(uint32_t), c->stream));
-        // wide complexes of <= 362 points run on u16 rank codes (half the per-wave distance matrix
-        // the scattered walk and pivot-search reads miss on): the narrow launches and the bucket
-        // pass first, then per slice of the wide list its codes (betti_rank_codes) and a wide launch
-        {
-            TimedLaunch t(c, "betti_vr", bytes, 0.0);
-            HIP_TRY(c, launch_betti(c->stream, pb, max_points, c->betti_slots,
-                                    max_points > 64 && !c16 ? &wl : nullptr, wide_waves, &fork));
-            if (c16) {
-                // slices of the wide list sized on the host from an upper bound of its length (the
-                // count pass's census of 65..kWideRegular-point complexes, which the host already
-                // holds), their lengths derived on the device from the bucket pass's wide_len: no
-                // host read, no stream synchronization
-                const int64_t nwide = given ? cnt : std::min<int64_t>(cnt, nw().wide_atoms);
-                if (nwide > 0) {
-                    const int64_t rstride = ((int64_t)max_points * (max_points - 1) / 2 + 63) / 64 * 64;
-                    int64_t slice = std::max<int64_t>(
-                        1, std::min<int64_t>({nwide, (int64_t(16) << 30) / (20 * rstride), INT32_MAX / rstride}));
-                    // The walk pass's per-complex outputs (matrix, lists: ~1.7 MB at 340 points), two
-                    // slices' worth within half of the HBM that is free or already theirs, <= 32 GB
-                    // (a quarter cut the slices below the reductions' 8,192 resident waves in a process
-                    // holding ~40 GB elsewhere, the bench's config-4 shard: 7-9 % slower at 10 A).
-                    // Slice q's walk pass (LDS- and issue-bound, one workgroup per CU) runs on the context
-                    // stream while slice q - 1's reductions (LDS-free, latency-bound) run on a second
-                    // stream: double-buffered codes and walk outputs, ordered by events
-                    const int64_t walk_bytes = prewalk ? betti_walk_out_bytes(max_points) : 0;
-                    const int nbuf = prewalk ? 2 : 1;
-                    if (prewalk) {
-                        size_t free_b = 0, total_b = 0;
-                        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-                        const int64_t wbudget = std::min<int64_t>(
-                            int64_t(32) << 30, std::max<int64_t>(int64_t(1) << 30, ((int64_t)free_b + (int64_t)c->b_walk.bytes) / 2));
-                        slice = std::max<int64_t>(1, std::min<int64_t>(slice, wbudget / (nbuf * walk_bytes)));
-                    }
-                    // equal slices: a short last slice leaves its launch's resident waves idle behind
-                    // a tail of single complexes
-                    slice = (nwide + (nwide + slice - 1) / slice - 1) / ((nwide + slice - 1) / slice);
-                    const size_t tmp_bytes = betti_rank_temp_bytes(slice, rstride);
-                    const size_t rank_buf = (8 * (size_t)slice * rstride + tmp_bytes + 255) / 256 * 256;
-                    const size_t walk_buf = ((size_t)walk_bytes * (size_t)slice + 255) / 256 * 256;
-                    if (prewalk) HIP_TRY(c, c->b_walk.ensure(walk_buf * nbuf));
-                    HIP_TRY(c, c->b_rank16.ensure(rank_buf * nbuf));
-                    const int64_t nsl = (nwide + slice - 1) / slice;
-                    HIP_TRY(c, c->b_rscal16.ensure(sizeof(uint32_t) * 2 * (size_t)nsl));
-                    uint32_t* sl = c->b_rscal16.as<uint32_t>();
-                    HIP_TRY(c, launch_slice_lengths(c->stream, &sc->wide_len, slice, nsl, sl));
-                    hipStream_t rs = c->stream;  // the reductions' stream
-                    if (prewalk && nsl > 1) {
-                        if (!c->rstream) {
-                            HIP_TRY(c, hipStreamCreateWithFlags(&c->rstream, hipStreamNonBlocking));
-                            for (int k = 0; k < 2; ++k) {
-                                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_walk[k], hipEventDisableTiming));
-                                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_red[k], hipEventDisableTiming));
-                            }
-                        }
-                        rs = c->rstream;
-                    }
-                    for (int64_t q = 0; q < nsl; ++q) {
-                        const int k = (int)(q % nbuf);
-                        uint32_t* codes = reinterpret_cast<uint32_t*>(c->b_rank16.as<uint8_t>() + k * rank_buf);
-                        uint32_t* sorted = codes + slice * rstride;
-                        BettiLaunch wb = pb;
-                        wb.wide_list = c->b_wlist.as<int32_t>() + q * slice;
-                        wb.wide_len = sl + 2 * q;
-                        wb.wide_queue = sl + 2 * q + 1;
-                        const int64_t ub = std::min<int64_t>(slice, nwide - q * slice);
-                        // buffer k was last read by slice q - 2's reductions
-                        if (rs != c->stream && q >= 2) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_red[k], 0));
-                        HIP_TRY(c, betti_rank_codes(c->stream, pb.lower, pb.tri_stride, pb.npoints, wb.wide_list, ub,
-                                                    rstride, codes, sorted, sorted + slice * rstride, tmp_bytes,
-                                                    wb.wide_len));
-                        wb.rank_codes = codes;
-                        wb.rank_sorted = sorted;
-                        wb.rank_stride = rstride;
-                        if (prewalk) {
-                            WalkOut wo = betti_walk_out_layout(max_points);
-                            uint8_t* p = c->b_walk.as<uint8_t>() + k * walk_buf;
-                            auto carve = [&](int64_t bytes_per_complex) {
-                                uint8_t* r = p;
-                                p += (size_t)bytes_per_complex * (size_t)slice;
-                                return r;
-                            };
-                            wo.dmat = reinterpret_cast<uint16_t*>(carve(2 * wo.dstride));
-                            wo.meta = reinterpret_cast<uint32_t*>(carve(32));
-                            wo.d0 = reinterpret_cast<float*>(carve(4 * wo.d0stride));
-                            wo.mce = reinterpret_cast<uint16_t*>(carve(2 * wo.mstride));
-                            wo.e1 = reinterpret_cast<uint64_t*>(carve(8 * (int64_t)wo.cap1));
-                            wo.cl = reinterpret_cast<uint32_t*>(carve(4 * (int64_t)wo.cap1));
-                            wo.ent = reinterpret_cast<uint64_t*>(carve(8 * (int64_t)wo.cap));
-                            wb.walk = wo;
-                            HIP_TRY(c, launch_betti_walk(c->stream, wb, ub, max_points));
-                        }
-                        if (rs != c->stream) {
-                            HIP_TRY(c, hipEventRecord(c->ev_walk[k], c->stream));
-                            HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_walk[k], 0));
-                        }
-                        HIP_TRY(c, launch_betti_wide(rs, wb, wl, (int)std::min<int64_t>(wide_waves, ub)));
-                        if (rs != c->stream) HIP_TRY(c, hipEventRecord(c->ev_red[k], rs));
-                    }
-                    if (rs != c->stream) {  // join: the retry launch and the outputs follow on the context stream
-                        HIP_TRY(c, hipEventRecord(c->ev_red[0], rs));
-                        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_red[0], 0));
-                    }
-                }
-            }
-        }
-        if (pb.force_retry) {
-            // test knob (no kernel checks it: a per-complex flag read cost 0.8 % of the narrow
-            // launch): every complex of the pass is listed for the retry launch, which overwrites
-            // its outputs
-            std::vector<int32_t> all((size_t)cnt);
-            for (int64_t i = 0; i < cnt; ++i) all[(size_t)i] = (int32_t)i;
-            const uint32_t n32 = (uint32_t)cnt;
-            HIP_TRY(c, hipMemcpyAsync(c->b_rlist.p, all.data(), sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice,
-                                      c->stream));
-            HIP_TRY(c, hipMemcpyAsync(&sc->retry_len, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, stream_sync(c));
-        }
-        // complexes whose reduction outgrew a kernel's workspace (the reference's Ripser has no
-        // caps, ripser.cpp:514-1269): reduced again with the big wide layout
-        const int nmax = std::max(max_points, 64);
-        const bool coded = nmax > kWideRegular;
-        HIP_TRY(c, c->b_rlist2.ensure(sizeof(int32_t) * (size_t)A));
-        int32_t* cur = c->b_rlist.as<int32_t>();
-        int32_t* nxt = c->b_rlist2.as<int32_t>();
-        int64_t nretry = -1;
-        int grow0 = 0;
-        if (!coded && c->dbg_big_log2 == 0) {
-            // Device-driven retry (complexes of up to kWideRegular points: the 5 A and 10 A paths):
-            // the launch reads the retry list's length on the device and its waves leave at once when
-            // nothing overflowed, so the pass never waits for the host. Its workspace (first growth
-            // level, >= 8 waves) is kept for the context's lifetime, its tables restored by every
-            // reduction; it takes at most an eighth of the HBM that is free or already its own, and
-            // 32 GB (288 GB per MI355X).
-            WideLayout big = betti_wide_layout(nmax, true);
-            if (c->big_budget == 0) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-                c->big_budget = std::min<int64_t>(int64_t(32) << 30, ((int64_t)free_b + (int64_t)c->b_big.bytes) / 8);
-            }
-            const int64_t waves =
-                std::min<int64_t>({c->big_budget / big.total, betti_wide_resident_waves(c->device, nmax), 32});
-            if (waves >= 8) {
-                if (c->big_nmax != nmax || c->big_waves < waves) {
-                    HIP_TRY(c, c->b_big.ensure((size_t)big.total * (size_t)waves));
-                    big.base = c->b_big.as<uint8_t>();
-                    HIP_TRY(c, betti_wide_init_scratch(c->stream, big, (int)waves));
-                    c->big_nmax = nmax;
-                    c->big_waves = (int)waves;
-                }
-                big.base = c->b_big.as<uint8_t>();
-                BettiLaunch rb = pb;
-                rb.rank_codes = nullptr;
-                rb.rank_sorted = nullptr;
-                // a complex that outgrows this level: the device entry points report DGN_ERR_CAPACITY
-                // at their next synchronizing call (no host read here); the host entry points list it
-                // for the growing levels below
-                rb.retry_list = async_report ? nullptr : nxt;
-                rb.retry_len = async_report ? nullptr : &sc->retry2_len;
-                rb.force_retry = 0;
-                rb.retried = bflags + kBFRetried;
-                rb.wide_list = c->b_rlist.as<int32_t>();
-                rb.wide_len = &sc->retry_len;
-                rb.wide_queue = &sc->retry_queue;
-                if (!async_report) HIP_TRY(c, hipMemsetAsync(&sc->retry2_len, 0, sizeof(uint32_t), c->stream));
-                {
-                    TimedLaunch t(c, "betti_retry", 0.0, 0.0);
-                    HIP_TRY(c, launch_betti_wide(c->stream, rb, big, (int)waves));
-                }
-                HIP_TRY(c, hipMemsetAsync(&sc->retry_len, 0, 2 * sizeof(uint32_t), c->stream));
-                if (async_report) return DGN_OK;
-                HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry2_len, &sc->retry2_len, sizeof(uint32_t),
-                                          hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, stream_sync(c));
-                nretry = c->host->s.retry2_len;
-                if (nretry == 0) return DGN_OK;
-                std::swap(cur, nxt);
-                grow0 = 1;
-            }
-        }
-        if (nretry < 0) {
-            // larger complexes: the retry workspace is sized by the number of complexes that
-            // overflowed (one host read of the list length)
-            HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry_len, &sc->retry_len, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                      c->stream));
-            HIP_TRY(c, stream_sync(c));
-            nretry = c->host->s.retry_len;
-            if (nretry == 0) return DGN_OK;
-        }
-        // complexes above kWideRegular points (listed by the bucket pass) run on rank codes
-        // (betti_rank_codes, the BIG / HUGE instantiations), in slices of at most 512 complexes.
-        // The tables grow with the complexes (the reference's Ripser has no caps): a complex that
-        // outgrows level `grow` is listed again and reduced at the next level, 4x the tables
-        c->big_nmax = 0;  // the workspace below is laid out per call
-        const int64_t rstride = ((int64_t)nmax * (nmax - 1) / 2 + 63) / 64 * 64;
-        for (int grow = grow0;; ++grow) {
-            const bool last = grow == kWideMaxGrow;
-            WideLayout big = betti_wide_layout(nmax, true, 0, grow, c->dbg_big_log2 ? c->dbg_big_log2 : 24);
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-            // (GIANT: 8.4 M distances per 4,096-point complex; a slice keeps its codes below 16 GB and
-            // its segmented-sort offsets in int32)
-            const int64_t slice = coded ? std::max<int64_t>(1, std::min<int64_t>({nretry, 512, INT32_MAX / rstride,
-                                                                                   (int64_t(16) << 30) / (8 * rstride)}))
-                                        : nretry;
-            const int64_t nsl = (nretry + slice - 1) / slice;
-            const size_t rank_bytes = coded ? betti_rank_temp_bytes(slice, rstride) + 8 * (size_t)slice * rstride : 0;
-            const int64_t budget =
-                (int64_t)(free_b / 2) + (int64_t)c->b_big.bytes + (int64_t)c->b_rank.bytes - (int64_t)rank_bytes;
-            const int64_t waves =
-                std::min<int64_t>({slice, budget / big.total, betti_wide_resident_waves(c->device, nmax)});
-            if (waves < 1)
-                return fail(c, DGN_ERR_CAPACITY, "capacity retry: no device memory for a " +
-                                                     std::to_string(big.total) + "-byte workspace");
-            HIP_TRY(c, c->b_big.ensure((size_t)big.total * (size_t)waves));
-            big.base = c->b_big.as<uint8_t>();
-            HIP_TRY(c, betti_wide_init_scratch(c->stream, big, (int)waves));
-            if (coded) HIP_TRY(c, c->b_rank.ensure(rank_bytes));
-            // per slice (length, queue), then the next level's list length
-            HIP_TRY(c, c->b_rscal.ensure(sizeof(uint32_t) * (2 * (size_t)nsl + 2)));
-            uint32_t* sl0 = c->b_rscal.as<uint32_t>();
-            uint32_t* next_len = sl0 + 2 * nsl;
-            std::vector<uint32_t> lens((size_t)nsl);
-            for (int64_t q = 0; q < nsl; ++q) lens[q] = (uint32_t)std::min<int64_t>(slice, nretry - q * slice);
-            HIP_TRY(c, hipMemsetAsync(sl0, 0, sizeof(uint32_t) * (2 * (size_t)nsl + 2), c->stream));
-            for (int64_t q = 0; q < nsl; ++q)
-                HIP_TRY(c, hipMemcpyAsync(sl0 + 2 * q, &lens[q], sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            BettiLaunch rb = pb;
-            rb.rank_codes = nullptr;  // set per slice below when coded
-            rb.rank_sorted = nullptr;
-            rb.retry_list = last ? nullptr : nxt;  // last level: a further overflow is DGN_ERR_CAPACITY
-            rb.retry_len = last ? nullptr : next_len;
-            rb.force_retry = 0;
-            rb.retried = bflags + kBFRetried;
-            for (int64_t q = 0; q < nsl; ++q) {
-                rb.wide_list = cur + q * slice;
-                if (coded) {
-                    uint32_t* codes = c->b_rank.as<uint32_t>();
-                    uint32_t* sorted = codes + slice * rstride;
-                    void* tmp = sorted + slice * rstride;
-                    HIP_TRY(c, betti_rank_codes(c->stream, pb.lower, pb.tri_stride, pb.npoints, rb.wide_list,
-                                                (int64_t)lens[q], rstride, codes, sorted, tmp,
-                                                rank_bytes - 8 * (size_t)slice * rstride));
-                    rb.rank_codes = codes;
-                    rb.rank_sorted = sorted;
-                    rb.rank_stride = rstride;
-                }
-                rb.wide_len = sl0 + 2 * q;
-                rb.wide_queue = sl0 + 2 * q + 1;
-                TimedLaunch t(c, "betti_retry", 0.0, 0.0);
-                HIP_TRY(c, launch_betti_wide(c->stream, rb, big, (int)std::min<int64_t>(waves, lens[q])));
-            }
-            HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry_len, next_len, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                      c->stream));
-            HIP_TRY(c, stream_sync(c));  // `lens` leaves scope; the next level's count
-            nretry = last ? 0 : c->host->s.retry_len;
-            if (nretry == 0) break;
-            std::swap(cur, nxt);
-        }
-        // the regular wide layout's tables are not touched; the big buffer is kept for reuse
-        HIP_TRY(c, hipMemsetAsync(&sc->retry_len, 0, 2 * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, stream_sync(c));
-        return DGN_OK;
+    return DGN_OK;
+}
+
+// complexes above 64 points: the wide kernel, one wave per complex with a per-wave scratch
+// (distance matrix, min-cofacet tables, sorted columns, pivot hash) sized for max_points. Sets the
+// regular wide layout and its wave count, and re-initialises the tables when the layout changed
+int plan_wide(dgn_ctx* c, int64_t A, BettiPass& P) {
+    const int wide_nmax = std::min(P.max_points, kWideRegular);  // larger: the coded retry launch
+    WideLayout wl = betti_wide_layout(wide_nmax, false, c->dbg_wide_cap, 0, 24, P.prewalk);
+    // as many waves as the device keeps resident (dynamic LDS sized by max_points), each with its
+    // own scratch, within half of the HBM that is free or already this workspace's (at least 8 GB):
+    // a changed wave count is a changed layout, which re-initialises every wave's tables
+    const int64_t budget = hbm_share(c->b_wide.bytes, 2, int64_t(8) << 30, INT64_MAX);
+    const int64_t resident = betti_wide_resident_waves(c->device, wide_nmax, P.c16, P.prewalk);
+    int wide_waves = (int)std::max<int64_t>(1, std::min<int64_t>({budget / wl.total, resident, A}));
+    if (c->dbg_wide_waves > 0 && c->dbg_wide_waves < wide_waves) wide_waves = c->dbg_wide_waves;  // A/B only
+    const size_t want = (size_t)wl.total * (size_t)wide_waves;
+    const bool grown = c->b_wide.bytes < want;
+    if (grown) HIP_TRY(c, c->b_wide.ensure(want));
+    wl.base = c->b_wide.as<uint8_t>();
+    if (grown || c->wide_nmax != wide_nmax || c->wide_waves != wide_waves || c->wide_cap != wl.na_cap ||
+        c->wide_pre != (int)P.prewalk) {
+        // the layout depends on max_points: every wave's pivot hash table starts empty (key 0)
+        // and its u16 min-cofacet tables "no cofacet" (0xFFFF); afterwards each reduction
+        // restores both for the entries it used
+        HIP_TRY(c, betti_wide_init_scratch(c->stream, wl, wide_waves));
+        c->wide_nmax = wide_nmax;
+        c->wide_waves = wide_waves;
+        c->wide_cap = wl.na_cap;
+        c->wide_pre = (int)P.prewalk;
+    }
+    HIP_TRY(c, c->b_wlist.ensure(sizeof(int32_t) * (size_t)A));
+    P.bl.wide_list = c->b_wlist.as<int32_t>();
+    P.wl = wl;
+    P.wide_waves = wide_waves;
+    return DGN_OK;
+}
+
+// the walk pass's outputs for a slice of `slice` complexes, carved from p
+WalkOut carve_walk_out(uint8_t* p, int64_t slice, int max_points) {
+    WalkOut wo = betti_walk_out_layout(max_points);
+    auto carve = [&](int64_t bytes_per_complex) {
+        uint8_t* r = p;
+        p += (size_t)bytes_per_complex * (size_t)slice;
+        return r;
     };
-    // triangles: floats per complex, padded to a multiple of 4 (16-byte aligned complexes)
-    const int64_t tri_stride = std::max<int64_t>(4, ((int64_t)max_points * (max_points - 1) / 2 + 3) / 4 * 4);
-    if (lower) {
+    wo.dmat = reinterpret_cast<uint16_t*>(carve(2 * wo.dstride));
+    wo.meta = reinterpret_cast<uint32_t*>(carve(32));
+    wo.d0 = reinterpret_cast<float*>(carve(4 * wo.d0stride));
+    wo.mce = reinterpret_cast<uint16_t*>(carve(2 * wo.mstride));
+    wo.e1 = reinterpret_cast<uint64_t*>(carve(8 * (int64_t)wo.cap1));
+    wo.cl = reinterpret_cast<uint32_t*>(carve(4 * (int64_t)wo.cap1));
+    wo.ent = reinterpret_cast<uint64_t*>(carve(8 * (int64_t)wo.cap));
+    return wo;
+}
+
+// Orders everything queued on `from` before what follows on `into`, on every exit of its scope
+// (an early error return included); no-op when the two are one stream. Errors are ignored, as in
+// ~TimedLaunch: the caller is already returning one, or the next call on the stream reports it.
+struct StreamJoin {
+    hipStream_t from, into;
+    hipEvent_t ev;
+    ~StreamJoin() {
+        if (from == into) return;
+        (void)hipEventRecord(ev, from);
+        (void)hipStreamWaitEvent(into, ev, 0);
+    }
+};
+
+// The u16-coded wide complexes (<= 362 points: half the per-wave distance matrix the scattered walk
+// and pivot-search reads miss on) of the pass `pb`, after its narrow launches and bucket pass: per
+// slice of the wide list its codes (betti_rank_codes), its walk pass and a wide launch. The slices
+// are sized on the host from nwide, an upper bound of the list's length (the count pass's census of
+// 65..kWideRegular-point complexes, which the host already holds), their lengths derived on the
+// device from the bucket pass's wide_len: no host read, no stream synchronization
+int run_coded_slices(dgn_ctx* c, const BettiPass& P, const BettiLaunch& pb, int64_t nwide) {
+    Scalars* sc = P.sc;
+    const int max_points = P.max_points;
+    const bool prewalk = P.prewalk;
+    const int64_t rstride = rank_stride(max_points);
+    int64_t slice =
+        std::max<int64_t>(1, std::min<int64_t>({nwide, (int64_t(16) << 30) / (20 * rstride), INT32_MAX / rstride}));
+    // The walk pass's per-complex outputs (matrix, lists: ~1.7 MB at 340 points), two
+    // slices' worth within half of the HBM that is free or already theirs, <= 32 GB
+    // (a quarter cut the slices below the reductions' 8,192 resident waves in a process
+    // holding ~40 GB elsewhere, the bench's config-4 shard: 7-9 % slower at 10 A).
+    // Slice q's walk pass (LDS- and issue-bound, one workgroup per CU) runs on the context
+    // stream while slice q - 1's reductions (LDS-free, latency-bound) run on a second
+    // stream: double-buffered codes and walk outputs, ordered by events
+    const int64_t walk_bytes = prewalk ? betti_walk_out_bytes(max_points) : 0;
+    const int nbuf = prewalk ? 2 : 1;
+    if (prewalk) {
+        const int64_t wbudget = hbm_share(c->b_walk.bytes, 2, int64_t(1) << 30, int64_t(32) << 30);
+        slice = std::max<int64_t>(1, std::min<int64_t>(slice, wbudget / (nbuf * walk_bytes)));
+    }
+    if (c->dbg_walk_slice > 0) slice = std::min<int64_t>(slice, c->dbg_walk_slice);  // tests only
+    // equal slices: a short last slice leaves its launch's resident waves idle behind
+    // a tail of single complexes
+    slice = (nwide + (nwide + slice - 1) / slice - 1) / ((nwide + slice - 1) / slice);
+    const size_t tmp_bytes = betti_rank_temp_bytes(slice, rstride);
+    const size_t rank_buf = (8 * (size_t)slice * rstride + tmp_bytes + 255) / 256 * 256;
+    const size_t walk_buf = ((size_t)walk_bytes * (size_t)slice + 255) / 256 * 256;
+    if (prewalk) HIP_TRY(c, c->b_walk.ensure(walk_buf * nbuf));
+    HIP_TRY(c, c->b_rank16.ensure(rank_buf * nbuf));
+    const int64_t nsl = (nwide + slice - 1) / slice;
+    HIP_TRY(c, c->b_rscal16.ensure(sizeof(uint32_t) * 2 * (size_t)nsl));
+    uint32_t* sl = c->b_rscal16.as<uint32_t>();
+    HIP_TRY(c, launch_slice_lengths(c->stream, &sc->wide_len, slice, nsl, sl));
+    hipStream_t rs = c->stream;  // the reductions' stream
+    if (prewalk && nsl > 1) {
+        if (!c->rstream) {
+            HIP_TRY(c, hipStreamCreateWithFlags(&c->rstream, hipStreamNonBlocking));
+            for (int k = 0; k < 2; ++k) {
+                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_walk[k], hipEventDisableTiming));
+                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_red[k], hipEventDisableTiming));
+            }
+        }
+        rs = c->rstream;
+    }
+    // the retry launch and the outputs' readers follow on the context stream: the reductions still
+    // read b_rank16, b_walk and b_wide and write the caller's outputs, so they are joined on every
+    // exit, a failed launch's early return included
+    const StreamJoin join{rs, c->stream, c->ev_red[0]};
+    for (int64_t q = 0; q < nsl; ++q) {
+        const int k = (int)(q % nbuf);
+        const RankBuf rb = carve_rank(c->b_rank16.as<uint8_t>() + k * rank_buf, slice, rstride);
+        BettiLaunch wb = pb;
+        wb.wide_list = c->b_wlist.as<int32_t>() + q * slice;
+        wb.wide_len = sl + 2 * q;
+        wb.wide_queue = sl + 2 * q + 1;
+        const int64_t ub = std::min<int64_t>(slice, nwide - q * slice);
+        // buffer k was last read by slice q - 2's reductions
+        if (rs != c->stream && q >= 2) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_red[k], 0));
+        HIP_TRY(c, betti_rank_codes(c->stream, pb.lower, pb.tri_stride, pb.npoints, wb.wide_list, ub, rstride,
+                                    rb.codes, rb.sorted, rb.tmp, tmp_bytes, wb.wide_len));
+        wb.rank_codes = rb.codes;
+        wb.rank_sorted = rb.sorted;
+        wb.rank_stride = rstride;
+        if (prewalk) {
+            wb.walk = carve_walk_out(c->b_walk.as<uint8_t>() + k * walk_buf, slice, max_points);
+            HIP_TRY(c, launch_betti_walk(c->stream, wb, ub, max_points));
+        }
+        if (rs != c->stream) {
+            HIP_TRY(c, hipEventRecord(c->ev_walk[k], c->stream));
+            HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_walk[k], 0));
+        }
+        HIP_TRY(c, launch_betti_wide(rs, wb, P.wl, (int)std::min<int64_t>(P.wide_waves, ub)));
+        if (rs != c->stream) HIP_TRY(c, hipEventRecord(c->ev_red[k], rs));
+    }
+    return DGN_OK;
+}
+
+// test knob DGN_DEBUG_FORCE_RETRY (no kernel checks it: a per-complex flag read cost 0.8 % of the
+// narrow launch): every complex of the pass is listed for the retry launch, which overwrites its
+// outputs
+int list_all_for_retry(dgn_ctx* c, const BettiPass& P, int64_t cnt) {
+    std::vector<int32_t> all((size_t)cnt);
+    for (int64_t i = 0; i < cnt; ++i) all[(size_t)i] = (int32_t)i;
+    const uint32_t n32 = (uint32_t)cnt;
+    HIP_TRY(c, hipMemcpyAsync(c->b_rlist.p, all.data(), sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&P.sc->retry_len, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, stream_sync(c));
+    return DGN_OK;
+}
+
+// where a pass's capacity retry stands: complexes whose reduction outgrew a kernel's workspace (the
+// reference's Ripser has no caps, ripser.cpp:514-1269) are reduced again with the big wide layout
+struct RetryState {
+    int nmax;            // the big layout's points
+    bool coded;          // above kWideRegular points: on rank codes
+    int32_t *cur, *nxt;  // the list to reduce, the list its overflows go to
+    int64_t len = -1;    // entries of cur (< 0: still on the device, sc->retry_len)
+    int grow = 0;        // the next host-driven level
+    bool done = false;   // nothing left for the host-driven levels
+};
+
+// Device-driven retry (complexes of up to kWideRegular points: the 5 A and 10 A paths):
+// the launch reads the retry list's length on the device and its waves leave at once when
+// nothing overflowed, so the pass never waits for the host. Its workspace (first growth
+// level, >= 8 waves) is kept for the context's lifetime, its tables restored by every
+// reduction; it takes at most an eighth of the HBM that is free or already its own, and
+// 32 GB, decided at the context's first use. Leaves r untouched when it does not apply (coded
+// complexes, a shrunk first level, no room for 8 waves); else r.done, or r at level 1 with the
+// list of the complexes that outgrew this one.
+int retry_on_device(dgn_ctx* c, const BettiPass& P, const BettiLaunch& pb, RetryState& r) {
+    if (r.coded || c->dbg_big_log2 != 0) return DGN_OK;
+    Scalars* sc = P.sc;
+    WideLayout big = betti_wide_layout(r.nmax, true);
+    if (c->big_budget == 0) c->big_budget = hbm_share(c->b_big.bytes, 8, 0, int64_t(32) << 30);
+    const int64_t waves =
+        std::min<int64_t>({c->big_budget / big.total, betti_wide_resident_waves(c->device, r.nmax), 32});
+    if (waves < 8) return DGN_OK;
+    if (c->big_nmax != r.nmax || c->big_waves < waves) {
+        HIP_TRY(c, c->b_big.ensure((size_t)big.total * (size_t)waves));
+        big.base = c->b_big.as<uint8_t>();
+        HIP_TRY(c, betti_wide_init_scratch(c->stream, big, (int)waves));
+        c->big_nmax = r.nmax;
+        c->big_waves = (int)waves;
+    }
+    big.base = c->b_big.as<uint8_t>();
+    BettiLaunch rb = pb;
+    rb.rank_codes = nullptr;
+    rb.rank_sorted = nullptr;
+    // a complex that outgrows this level: the device entry points report DGN_ERR_CAPACITY
+    // at their next synchronizing call (no host read here); the host entry points list it
+    // for the growing levels (retry_growing)
+    rb.retry_list = P.async_report ? nullptr : r.nxt;
+    rb.retry_len = P.async_report ? nullptr : &sc->retry2_len;
+    rb.force_retry = 0;
+    rb.retried = P.bflags + kBFRetried;
+    rb.wide_list = c->b_rlist.as<int32_t>();
+    rb.wide_len = &sc->retry_len;
+    rb.wide_queue = &sc->retry_queue;
+    if (!P.async_report) HIP_TRY(c, hipMemsetAsync(&sc->retry2_len, 0, sizeof(uint32_t), c->stream));
+    {
+        TimedLaunch t(c, "betti_retry", 0.0, 0.0);
+        HIP_TRY(c, launch_betti_wide(c->stream, rb, big, (int)waves));
+    }
+    HIP_TRY(c, hipMemsetAsync(&sc->retry_len, 0, 2 * sizeof(uint32_t), c->stream));
+    r.done = P.async_report;
+    if (r.done) return DGN_OK;
+    HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry2_len, &sc->retry2_len, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, stream_sync(c));
+    r.len = c->host->s.retry2_len;
+    r.done = r.len == 0;
+    std::swap(r.cur, r.nxt);
+    r.grow = 1;
+    return DGN_OK;
+}
+
+// Host-driven retry levels. Complexes above kWideRegular points (listed by the bucket pass) run on
+// rank codes (betti_rank_codes, the BIG / HUGE instantiations), in slices of at most 512 complexes.
+// The tables grow with the complexes (the reference's Ripser has no caps): a complex that
+// outgrows level `grow` is listed again and reduced at the next level, 4x the tables
+int retry_growing(dgn_ctx* c, const BettiPass& P, const BettiLaunch& pb, RetryState r) {
+    Scalars* sc = P.sc;
+    int64_t nretry = r.len;
+    if (nretry < 0) {
+        // larger complexes: the retry workspace is sized by the number of complexes that
+        // overflowed (one host read of the list length)
+        HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry_len, &sc->retry_len, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, stream_sync(c));
+        nretry = c->host->s.retry_len;
+        if (nretry == 0) return DGN_OK;
+    }
+    c->big_nmax = 0;  // the workspace below is laid out per call
+    const int nmax = r.nmax;
+    const bool coded = r.coded;
+    const int64_t rstride = rank_stride(nmax);
+    for (int grow = r.grow;; ++grow) {
+        const bool last = grow == kWideMaxGrow;
+        WideLayout big = betti_wide_layout(nmax, true, 0, grow, c->dbg_big_log2 ? c->dbg_big_log2 : 24);
+        // (GIANT: 8.4 M distances per 4,096-point complex; a slice keeps its codes below 16 GB and
+        // its segmented-sort offsets in int32)
+        const int64_t slice = coded ? std::max<int64_t>(1, std::min<int64_t>({nretry, 512, INT32_MAX / rstride,
+                                                                               (int64_t(16) << 30) / (8 * rstride)}))
+                                    : nretry;
+        const int64_t nsl = (nretry + slice - 1) / slice;
+        const size_t rank_bytes = coded ? betti_rank_temp_bytes(slice, rstride) + 8 * (size_t)slice * rstride : 0;
+        // not hbm_share's rule: half of the free HBM plus all that the two workspaces already hold,
+        // less the rank buffer this level needs
+        const int64_t budget = hbm_free() / 2 + (int64_t)c->b_big.bytes + (int64_t)c->b_rank.bytes - (int64_t)rank_bytes;
+        const int64_t waves = std::min<int64_t>({slice, budget / big.total, betti_wide_resident_waves(c->device, nmax)});
+        if (waves < 1)
+            return fail(c, DGN_ERR_CAPACITY,
+                        "capacity retry: no device memory for a " + std::to_string(big.total) + "-byte workspace");
+        HIP_TRY(c, c->b_big.ensure((size_t)big.total * (size_t)waves));
+        big.base = c->b_big.as<uint8_t>();
+        HIP_TRY(c, betti_wide_init_scratch(c->stream, big, (int)waves));
+        if (coded) HIP_TRY(c, c->b_rank.ensure(rank_bytes));
+        // per slice (length, queue), then the next level's list length
+        HIP_TRY(c, c->b_rscal.ensure(sizeof(uint32_t) * (2 * (size_t)nsl + 2)));
+        uint32_t* sl0 = c->b_rscal.as<uint32_t>();
+        uint32_t* next_len = sl0 + 2 * nsl;
+        std::vector<uint32_t> lens((size_t)nsl);
+        for (int64_t q = 0; q < nsl; ++q) lens[q] = (uint32_t)std::min<int64_t>(slice, nretry - q * slice);
+        HIP_TRY(c, hipMemsetAsync(sl0, 0, sizeof(uint32_t) * (2 * (size_t)nsl + 2), c->stream));
+        for (int64_t q = 0; q < nsl; ++q)
+            HIP_TRY(c, hipMemcpyAsync(sl0 + 2 * q, &lens[q], sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        BettiLaunch rb = pb;
+        rb.rank_codes = nullptr;  // set per slice below when coded
+        rb.rank_sorted = nullptr;
+        rb.retry_list = last ? nullptr : r.nxt;  // last level: a further overflow is DGN_ERR_CAPACITY
+        rb.retry_len = last ? nullptr : next_len;
+        rb.force_retry = 0;
+        rb.retried = P.bflags + kBFRetried;
+        for (int64_t q = 0; q < nsl; ++q) {
+            rb.wide_list = r.cur + q * slice;
+            if (coded) {
+                const RankBuf k = carve_rank(c->b_rank.p, slice, rstride);
+                HIP_TRY(c, betti_rank_codes(c->stream, pb.lower, pb.tri_stride, pb.npoints, rb.wide_list,
+                                            (int64_t)lens[q], rstride, k.codes, k.sorted, k.tmp,
+                                            rank_bytes - 8 * (size_t)slice * rstride));
+                rb.rank_codes = k.codes;
+                rb.rank_sorted = k.sorted;
+                rb.rank_stride = rstride;
+            }
+            rb.wide_len = sl0 + 2 * q;
+            rb.wide_queue = sl0 + 2 * q + 1;
+            TimedLaunch t(c, "betti_retry", 0.0, 0.0);
+            HIP_TRY(c, launch_betti_wide(c->stream, rb, big, (int)std::min<int64_t>(waves, lens[q])));
+        }
+        HIP_TRY(c, hipMemcpyAsync(&c->host->s.retry_len, next_len, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, stream_sync(c));  // `lens` leaves scope; the next level's count
+        nretry = last ? 0 : c->host->s.retry_len;
+        if (nretry == 0) break;
+        std::swap(r.cur, r.nxt);
+    }
+    // the regular wide layout's tables are not touched; the big buffer is kept for reuse
+    HIP_TRY(c, hipMemsetAsync(&sc->retry_len, 0, 2 * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, stream_sync(c));
+    return DGN_OK;
+}
+
+// Betti pass over complexes [c0, c0 + cnt) of the call, whose triangles are in `tri`
+int vr_pass(dgn_ctx* c, const BettiPass& P, int64_t c0, int64_t cnt, const float* tri, int64_t tstride,
+            const int32_t* np, const double* w, double bytes) {
+    Scalars* sc = P.sc;
+    BettiLaunch pb = P.bl;
+    pb.lower = tri;
+    pb.npoints = np;
+    pb.weight = w;
+    pb.tri_stride = tstride;
+    pb.num_atoms = cnt;
+    pb.features = pb.features ? pb.features + 35 * c0 : nullptr;
+    pb.counts = pb.counts ? pb.counts + 4 * c0 : nullptr;
+    pb.pairs_out = pb.pairs_out ? pb.pairs_out + c0 * 3 * (int64_t)pb.pair_cap * 2 : nullptr;
+    static_assert(offsetof(Scalars, dense_queue) - offsetof(Scalars, work_counter) == 8 * sizeof(uint32_t),
+                  "queue and list counters are contiguous");
+    HIP_TRY(c, hipMemsetAsync(&sc->work_counter, 0, 9 * sizeof(uint32_t), c->stream));
+    {
+        // the narrow launches and the bucket pass first (with the f32 wide launch), then the u16-coded
+        // wide complexes in slices
+        TimedLaunch t(c, "betti_vr", bytes, 0.0);
+        HIP_TRY(c, launch_betti(c->stream, pb, P.max_points, c->betti_slots,
+                                P.max_points > 64 && !P.c16 ? &P.wl : nullptr, P.wide_waves, &P.fork));
+        const int64_t nwide = std::min<int64_t>(cnt, P.wide_census);
+        if (P.c16 && nwide > 0)
+            if (int st = run_coded_slices(c, P, pb, nwide)) return st;
+    }
+    if (pb.force_retry)
+        if (int st = list_all_for_retry(c, P, cnt)) return st;
+    HIP_TRY(c, c->b_rlist2.ensure(sizeof(int32_t) * (size_t)P.bl.num_atoms));
+    RetryState r{};
+    r.nmax = std::max(P.max_points, 64);
+    r.coded = r.nmax > kWideRegular;
+    r.cur = c->b_rlist.as<int32_t>();
+    r.nxt = c->b_rlist2.as<int32_t>();
+    if (int st = retry_on_device(c, P, pb, r)) return st;
+    return r.done ? DGN_OK : retry_growing(c, P, pb, r);
+}
+
+int betti_impl(dgn_ctx* c, const BettiJob& job) {
+    const dgn_batch* b = job.batch;
+    const bool given = job.clouds || job.lower;
+    const int64_t A = given ? job.count : b->num_atoms;
+    if (A == 0) return DGN_OK;
+    GraphWork& nw = job.reuse_graph ? c->gw : c->bw;  // the neighbour pass of atom-centred complexes
+    BettiPass P;
+    P.max_points = job.stride;
+    P.wide_census = A;
+    P.async_report = job.async_report;
+    if (!given) {
+        // NeighborList(rc, SIZE_MAX) counts (betti_features.cpp:107): the largest local complex,
+        // sum n^2 for the byte accounting, the per-atom weights
+        // dgn_dev_graph_betti: the graph pass's count at the same cutoff already holds every
+        // neighbour within rc (NeighborList(rc, K) and NeighborList(rc, SIZE_MAX) see the same
+        // candidates, neighbor_list.cpp:27-66); its per-atom counts, hit masks, cell lists and
+        // weights serve the Betti search unchanged
+        if (!job.reuse_graph) {
+            int64_t E = 0;
+            int st = graph_count_impl(c, b, job.rc, UINT64_MAX, 1e-10, &E, true);
+            if (st) return st;
+        }
+        P.max_points = (int)nw.max_candidates + 1;
+        P.wide_census = nw.wide_atoms;
+    }
+    const int max_points = P.max_points;
+    // caller-given triangles (one connected component at a time, dgn_host_persistence's split) reach
+    // the GIANT instantiation; clouds and atom-centred complexes stop at the distance kernels' 2,048
+    const int envelope = job.lower ? kWideGiantPoints : betti_max_points();
+    if (max_points > envelope)
+        return fail(c, DGN_ERR_UNSUPPORTED,
+                    "local complex with " + std::to_string(max_points) + " points exceeds the " +
+                        std::to_string(envelope) + "-point kernel envelope (see DESIGN.md)");
+    P.c16 = c->dbg_wide_c16 && max_points > 64 && max_points <= kC16MaxPoints;
+    P.prewalk = P.c16 && c->dbg_wide_walk;
+    if (int st = betti_prepare(c, job, A, P)) return st;
+    if (max_points > 64)
+        if (int st = plan_wide(c, A, P)) return st;
+    HIP_TRY(c, c->b_rlist.ensure(sizeof(int32_t) * (size_t)A));
+    P.bl.retry_list = c->b_rlist.as<int32_t>();
+    // triangles: floats per complex
+    const int64_t tstride = std::max<int64_t>(4, tri_stride(max_points));
+    if (job.lower) {
         // caller-given triangles: the Betti pass alone
-        int st = vr_pass(0, A, lower, (int64_t)cloud_stride * (cloud_stride - 1) / 2, npoints, nullptr, 0.0);
+        int st = vr_pass(c, P, 0, A, job.lower, (int64_t)job.stride * (job.stride - 1) / 2, job.npoints, nullptr, 0.0);
         if (st) return st;
     } else {
         // distance pass (f64 VALU pairs; matrix cores above 64 points) + Betti pass per chunk of complexes; the triangle buffer is
         // bounded (~16 GB of the 288 GB HBM) so arbitrarily large shards stream through it
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(A, (int64_t(16) << 30) / (4 * tri_stride)));
-        HIP_TRY(c, c->b_lower.ensure(sizeof(float) * (size_t)(chunk * tri_stride)));
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(A, (int64_t(16) << 30) / (4 * tstride)));
+        HIP_TRY(c, c->b_lower.ensure(sizeof(float) * (size_t)(chunk * tstride)));
         HIP_TRY(c, c->b_np.ensure(sizeof(int32_t) * (size_t)chunk));
         HIP_TRY(c, c->b_w.ensure(sizeof(double) * (size_t)chunk));
         // per-complex averages over the batch: points n (sum n = E + A), sum n^2 from the count pass
-        const double En = given ? 0.0 : nw().sum_m, An = (double)A;
-        const double sum_n2 = given ? 0.0 : nw().sum_sq;
-        const GraphLaunch g = given ? GraphLaunch{} : graph_launch(nw(), b, rc, 1e-10, UINT64_MAX, true);
+        const double En = given ? 0.0 : nw.sum_m, An = (double)A;
+        const double sum_n2 = given ? 0.0 : nw.sum_sq;
+        const GraphLaunch g = given ? GraphLaunch{} : graph_launch(nw, b, job.rc, 1e-10, UINT64_MAX, true);
         for (int64_t c0 = 0; c0 < A; c0 += chunk) {
             const int64_t cnt = std::min<int64_t>(chunk, A - c0);
             const double f = (double)cnt / An;
@@ -864,28 +976,28 @@ int betti_impl(dgn_ctx* c, const dgn_batch* b, double rc, double* features, int3
                 const double bytes = given ? 0.0 : f * (24 * An + 2 * (sum_n2 - (En + An)) + 4 * An);
                 TimedLaunch t(c, "betti_dist", bytes, given ? 0.0 : f * 6.0 * sum_n2);
                 if (given) {
-                    BettiLaunch db = bl;
-                    db.tri_stride = tri_stride;
+                    BettiLaunch db = P.bl;
+                    db.tri_stride = tstride;
                     DistLaunch dl{c0, cnt, c->b_lower.as<float>(), c->b_np.as<int32_t>(), c->b_w.as<double>()};
                     HIP_TRY(c, launch_betti_dist(c->stream, db, dl));
                 } else {
-                    HIP_TRY(c, launch_betti_dist_search(c->stream, g, c0, cnt, max_points, tri_stride,
-                                                        nw().counts.as<int32_t>(), c->b_lower.as<float>(),
-                                                        c->b_np.as<int32_t>(), bflags + kBFSearch));
+                    HIP_TRY(c, launch_betti_dist_search(c->stream, g, c0, cnt, max_points, tstride,
+                                                        nw.counts.as<int32_t>(), c->b_lower.as<float>(),
+                                                        c->b_np.as<int32_t>(), P.bflags + kBFSearch));
                 }
             }
             // Betti pass: triangles in, 35 f64 + 4 i32 out
             const double bytes = given ? 0.0 : f * (2 * (sum_n2 - (En + An)) + 12 * An + An * (35 * 8 + 16));
-            const double* w = given ? c->b_w.as<double>() : (b->species ? nw().weight.as<double>() + c0 : nullptr);
-            int st = vr_pass(c0, cnt, c->b_lower.as<float>(), tri_stride, c->b_np.as<int32_t>(), w, bytes);
+            const double* w = given ? c->b_w.as<double>() : (b->species ? nw.weight.as<double>() + c0 : nullptr);
+            int st = vr_pass(c, P, c0, cnt, c->b_lower.as<float>(), tstride, c->b_np.as<int32_t>(), w, bytes);
             if (st) return st;
         }
     }
     // the pass's flags travel to the host behind its work; the device entry points return here
     // (asynchronous: the next synchronizing call reports them), the host ones wait and report
-    HIP_TRY(c, hipMemcpyAsync(c->host->betti_flags, bflags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->host->betti_flags, P.bflags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     c->betti_pending = true;
-    if (async_report) return DGN_OK;
+    if (job.async_report) return DGN_OK;
     HIP_TRY(c, stream_sync(c));
     return take_flags(c);
 }
@@ -1003,6 +1115,7 @@ int dgn_ctx_set_debug(dgn_ctx* c, int knob, int value) {
         case DGN_DEBUG_WIDE_C16: c->dbg_wide_c16 = value != 0; return DGN_OK;
         case DGN_DEBUG_WIDE_WALK: c->dbg_wide_walk = value != 0; return DGN_OK;
         case DGN_DEBUG_SPLIT_CHUNK: c->dbg_split_chunk = value > 0 ? value : 0; return DGN_OK;
+        case DGN_DEBUG_WALK_SLICE: c->dbg_walk_slice = value > 0 ? value : 0; return DGN_OK;
         case DGN_DEBUG_WIDE_CAP: c->dbg_wide_cap = value > 0 ? value : 0; return DGN_OK;
         case DGN_DEBUG_BIG_LOG2: c->dbg_big_log2 = value > 0 && value < 24 ? value : 0; return DGN_OK;
         case DGN_DEBUG_EMIT_CHUNK: c->dbg_emit_chunk = value > 0 ? value : 0; return DGN_OK;
@@ -1020,13 +1133,11 @@ int dgn_debug_retry_count(dgn_ctx* c, int64_t* out) {
     if (!c || !out) return DGN_ERR_ARG;
     *out = 0;
     if (!c->bflags.p) return DGN_OK;
-    uint32_t v = 0;
     HIP_TRY(c, hipMemcpyAsync(&c->host->pad, c->bflags.as<uint32_t>() + kBFRetried, sizeof(uint32_t),
                               hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->bflags.as<uint32_t>() + kBFRetried, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(c, stream_sync(c));
-    v = c->host->pad;
-    *out = v;
+    *out = c->host->pad;
     return take_flags(c);
 }
 
@@ -1137,27 +1248,15 @@ int dgn_host_graph(dgn_ctx* c, const dgn_batch* h, const dgn_graph_params* p, dg
     const size_t rbf_elem = p->rbf_dtype == DGN_F64 ? 8 : 4;
     const int64_t A = h->num_atoms;
     DevBuf rp, col, dist, disp, rbf;
-    auto cleanup = [&]() {
-        rp.release();
-        col.release();
-        dist.release();
-        disp.release();
-        rbf.release();
-    };
     hipError_t e;
     if ((e = rp.ensure(8 * (A + 1))) || (e = col.ensure(4 * std::max<int64_t>(E, 1))) ||
         (e = dist.ensure(8 * std::max<int64_t>(E, 1))) ||
         (p->write_displacement && (e = disp.ensure(24 * std::max<int64_t>(E, 1)))) ||
-        (nb && (e = rbf.ensure(rbf_elem * nb * std::max<int64_t>(E, 1))))) {
-        cleanup();
+        (nb && (e = rbf.ensure(rbf_elem * nb * std::max<int64_t>(E, 1)))))
         return hip_fail(c, e, "dgn_host_graph: device allocation");
-    }
     if (A == 0) HIP_TRY(c, hipMemsetAsync(rp.p, 0, 8, c->stream));
     dgn_graph_out o{col.as<int32_t>(), dist.as<double>(), disp.as<double>(), rbf.p};
-    if ((st = dgn_dev_graph_emit(c, &d, p, rp.as<int64_t>(), &o)) || (st = check_emit_flag(c))) {
-        cleanup();
-        return st;
-    }
+    if ((st = dgn_dev_graph_emit(c, &d, p, rp.as<int64_t>(), &o)) || (st = check_emit_flag(c))) return st;
     dgn_graph_result* r = new dgn_graph_result();
     std::memset(r, 0, sizeof(*r));
     r->num_atoms = A;
@@ -1174,7 +1273,6 @@ int dgn_host_graph(dgn_ctx* c, const dgn_batch* h, const dgn_graph_params* p, dg
     if (!e && E) e = hipMemcpy(r->distance, dist.p, 8 * E, hipMemcpyDeviceToHost);
     if (!e && E && r->displacement) e = hipMemcpy(r->displacement, disp.p, 24 * E, hipMemcpyDeviceToHost);
     if (!e && E && r->rbf) e = hipMemcpy(r->rbf, rbf.p, rbf_elem * nb * E, hipMemcpyDeviceToHost);
-    cleanup();
     if (e) {
         dgn_graph_result_free(r);
         return hip_fail(c, e, "dgn_host_graph: copy back");
@@ -1197,7 +1295,13 @@ int dgn_dev_betti(dgn_ctx* c, const dgn_batch* b, const dgn_betti_params* p, dou
     if (!c || !p || !batch_ok(b) || !b->species || !features || !(p->r_cutoff > 0))
         return fail(c, DGN_ERR_ARG, "dgn_dev_betti: bad args");
     HIP_TRY(c, hipSetDevice(c->device));
-    return betti_impl(c, b, p->r_cutoff, features, counts, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, false, true);
+    BettiJob job;
+    job.batch = b;
+    job.rc = p->r_cutoff;
+    job.features = features;
+    job.counts = counts;
+    job.async_report = true;
+    return betti_impl(c, job);
 }
 
 int dgn_dev_graph_betti(dgn_ctx* c, const dgn_batch* b, const dgn_graph_params* p, int64_t* row_ptr,
@@ -1211,9 +1315,15 @@ int dgn_dev_graph_betti(dgn_ctx* c, const dgn_batch* b, const dgn_graph_params* 
     if (st) return st;
     // one neighbour count for both passes when the cutoffs agree (the bench's config: rc 5 / 5)
     // (the 1/count(species) weights are reused only for the species array the count saw)
-    const bool reuse = bp->r_cutoff == p->r_cutoff && p->epsilon == 1e-10 && c->gw.has_weight &&
-                       c->gw.species == b->species;
-    return betti_impl(c, b, bp->r_cutoff, features, counts, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, reuse, true);
+    BettiJob job;
+    job.batch = b;
+    job.rc = bp->r_cutoff;
+    job.features = features;
+    job.counts = counts;
+    job.reuse_graph = bp->r_cutoff == p->r_cutoff && p->epsilon == 1e-10 && c->gw.has_weight &&
+                      c->gw.species == b->species;
+    job.async_report = true;
+    return betti_impl(c, job);
 }
 
 int dgn_dev_node_features(dgn_ctx* c, const dgn_batch* b, const double* embed, int32_t num_keys, int32_t D,
@@ -1363,19 +1473,19 @@ int dgn_debug_betti_clouds(dgn_ctx* c, const dgn_batch* h, double rc, int64_t fi
         return fail(c, DGN_ERR_CAPACITY, "dgn_debug_betti_clouds: a complex has " +
                                              std::to_string(c->bw.max_candidates + 1) + " points");
     const int64_t tri = (int64_t)max_points * (max_points - 1) / 2;
-    const int64_t tri_stride = std::max<int64_t>(4, (tri + 3) / 4 * 4);
+    const int64_t tstride = std::max<int64_t>(4, tri_stride(max_points));
     DevBuf dl, dn, dk;
     hipError_t e;
-    if ((e = dl.ensure(4 * (size_t)(count * tri_stride))) || (e = dn.ensure(4 * (size_t)count)) ||
+    if ((e = dl.ensure(4 * (size_t)(count * tstride))) || (e = dn.ensure(4 * (size_t)count)) ||
         (e = dk.ensure(8 * (size_t)(count * max_points))))
         return hip_fail(c, e, "dgn_debug_betti_clouds: allocation");
-    HIP_TRY(c, hipMemsetAsync(dl.p, 0, 4 * (size_t)(count * tri_stride), c->stream));
+    HIP_TRY(c, hipMemsetAsync(dl.p, 0, 4 * (size_t)(count * tstride), c->stream));
     HIP_TRY(c, hipMemsetAsync(dk.p, 0, 8 * (size_t)(count * max_points), c->stream));
     HIP_TRY(c, c->scalars.ensure(sizeof(Scalars)));
     Scalars* sc = c->scalars.as<Scalars>();
     HIP_TRY(c, hipMemsetAsync(&sc->graph_flag, 0, sizeof(uint32_t), c->stream));
     const GraphLaunch g = graph_launch(c->bw, &d, rc, 1e-10, UINT64_MAX, true);
-    HIP_TRY(c, launch_betti_dist_search(c->stream, g, first, count, max_points, tri_stride, c->bw.counts.as<int32_t>(),
+    HIP_TRY(c, launch_betti_dist_search(c->stream, g, first, count, max_points, tstride, c->bw.counts.as<int32_t>(),
                                         dl.as<float>(), dn.as<int32_t>(), &sc->graph_flag, dk.as<uint64_t>(),
                                         max_points));
     HIP_TRY(c, hipMemcpyAsync(&c->host->s.graph_flag, &sc->graph_flag, sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -1383,12 +1493,12 @@ int dgn_debug_betti_clouds(dgn_ctx* c, const dgn_batch* h, double rc, int64_t fi
     HIP_TRY(c, stream_sync(c));
     if (c->host->s.graph_flag)
         return fail(c, DGN_ERR_INTERNAL, "dgn_debug_betti_clouds: search disagreed with the count pass");
-    std::vector<float> tmp((size_t)(count * tri_stride));
+    std::vector<float> tmp((size_t)(count * tstride));
     if ((e = hipMemcpy(tmp.data(), dl.p, 4 * tmp.size(), hipMemcpyDeviceToHost)) ||
         (e = hipMemcpy(npoints, dn.p, 4 * (size_t)count, hipMemcpyDeviceToHost)) ||
         (keys && (e = hipMemcpy(keys, dk.p, 8 * (size_t)(count * max_points), hipMemcpyDeviceToHost))))
         return hip_fail(c, e, "dgn_debug_betti_clouds: copy back");
-    for (int64_t i = 0; i < count; ++i) std::memcpy(lower + i * tri, tmp.data() + i * tri_stride, 4 * (size_t)tri);
+    for (int64_t i = 0; i < count; ++i) std::memcpy(lower + i * tri, tmp.data() + i * tstride, 4 * (size_t)tri);
     return DGN_OK;
 }
 
@@ -1403,26 +1513,25 @@ static int persistence_split(dgn_ctx* c, const double* d_clouds, const float* d_
                              const int32_t* npoints, int64_t C, int32_t max_points, double threshold, float* pairs,
                              int32_t cap, std::vector<int32_t>& kk) {
     const int64_t tri_in = (int64_t)max_points * (max_points - 1) / 2;  // caller-given packing
-    const int64_t tri_stride = (tri_in + 3) / 4 * 4;
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(C, (int64_t(8) << 30) / (4 * tri_stride)));
+    const int64_t tstride = tri_stride(max_points);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(C, (int64_t(8) << 30) / (4 * tstride)));
     if (c->dbg_split_chunk > 0) chunk = std::min<int64_t>(chunk, c->dbg_split_chunk);  // tests only
     DevBuf tri, lab, dmap, doff, dsize, dsrc, sub, snp, spairs, scnt;
-    if (d_clouds) HIP_TRY(c, tri.ensure(4 * (size_t)(chunk * tri_stride)));
+    if (d_clouds) HIP_TRY(c, tri.ensure(4 * (size_t)(chunk * tstride)));
     HIP_TRY(c, lab.ensure(4 * (size_t)(chunk * max_points)));
     std::vector<int32_t> labels((size_t)(chunk * max_points));
     std::fill(kk.begin(), kk.end(), 0);
     for (int64_t c0 = 0; c0 < C; c0 += chunk) {
         const int64_t cnt = std::min<int64_t>(chunk, C - c0);
         const float* T = d_lower ? d_lower + c0 * tri_in : tri.as<float>();
-        const int64_t ts = d_lower ? tri_in : tri_stride;
-        if (d_clouds) HIP_TRY(c, launch_big_gram(c->stream, d_clouds, max_points, d_np, c0, cnt, tri.as<float>(), tri_stride));
+        const int64_t ts = d_lower ? tri_in : tstride;
+        if (d_clouds) HIP_TRY(c, launch_big_gram(c->stream, d_clouds, max_points, d_np, c0, cnt, tri.as<float>(), tstride));
         HIP_TRY(c, launch_components(c->stream, T, ts, d_np, c0, cnt, (float)threshold, lab.as<int32_t>(), max_points));
         HIP_TRY(c, hipMemcpyAsync(labels.data(), lab.p, 4 * (size_t)(cnt * max_points), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, stream_sync(c));
         // components (a root is its component's smallest vertex): vertex lists in ascending order
         std::vector<int32_t> map, src, size;
         std::vector<int64_t> off;
-        int32_t smax = 1;
         for (int64_t i = 0; i < cnt; ++i) {
             const int32_t n = npoints[c0 + i];
             const int32_t* L = labels.data() + i * max_points;
@@ -1444,7 +1553,6 @@ static int persistence_split(dgn_ctx* c, const double* d_clouds, const float* d_
                 off.push_back((int64_t)map.size());
                 size.push_back(count[(size_t)r]);
                 src.push_back((int32_t)i);
-                smax = std::max(smax, count[(size_t)r]);
                 map.resize(map.size() + (size_t)count[(size_t)r]);
             }
             std::vector<int32_t> fill((size_t)n, 0);
@@ -1455,7 +1563,6 @@ static int persistence_split(dgn_ctx* c, const double* d_clouds, const float* d_
         }
         const int64_t nsub = (int64_t)size.size();
         if (nsub == 0) continue;
-        (void)smax;
         // Components in groups of similar size (largest first), each group one Betti pass whose
         // triangle stride and pair capacity are its largest member's -- not the chunk's: a cloud with
         // one 2,000-point cluster and thousands of 2-point components would otherwise give every
@@ -1496,9 +1603,16 @@ static int persistence_split(dgn_ctx* c, const double* d_clouds, const float* d_
             HIP_TRY(c, hipMemcpyAsync(snp.p, gsize.data(), 4 * (size_t)gn, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(c, launch_gather_sub(c->stream, T, ts, dsrc.as<int32_t>(), doff.as<int64_t>(), dsize.as<int32_t>(),
                                          dmap.as<int32_t>(), gn, sub.as<float>(), gstride));
-            int st = betti_impl(c, nullptr, threshold, nullptr, scnt.as<int32_t>(), nullptr, snp.as<int32_t>(),
-                                std::max<int32_t>(gmax, 2), gn, spairs.as<float>(), gcap, sub.as<float>());
-            if (st) return st;
+            BettiJob job;
+            job.lower = sub.as<float>();
+            job.npoints = snp.as<int32_t>();
+            job.stride = std::max<int32_t>(gmax, 2);
+            job.count = gn;
+            job.rc = threshold;
+            job.counts = scnt.as<int32_t>();
+            job.pairs = spairs.as<float>();
+            job.pair_cap = gcap;
+            if (int st = betti_impl(c, job)) return st;
             std::vector<int32_t> sk(4 * (size_t)gn);
             std::vector<float> sp(2 * 3 * (size_t)gn * gcap);
             HIP_TRY(c, hipMemcpy(sk.data(), scnt.p, 16 * (size_t)gn, hipMemcpyDeviceToHost));
@@ -1551,10 +1665,19 @@ static int host_persistence_common(dgn_ctx* c, const double* clouds, const float
     HIP_TRY(c, hipMemcpy(dn.p, npoints, 4 * (size_t)C, hipMemcpyHostToDevice));
     std::vector<int32_t> kk(4 * C);
     const bool split = max_points > kWideMaxPoints;  // complexes above the kernels' envelope
-    int st = split ? persistence_split(c, clouds ? dc.as<double>() : nullptr, clouds ? nullptr : dc.as<float>(),
-                                       dn.as<int32_t>(), npoints, C, max_points, threshold, pairs, cap, kk)
-                   : betti_impl(c, nullptr, threshold, nullptr, dk.as<int32_t>(), clouds ? dc.as<double>() : nullptr,
-                                dn.as<int32_t>(), max_points, C, dp.as<float>(), cap, clouds ? nullptr : dc.as<float>());
+    BettiJob job;
+    job.clouds = clouds ? dc.as<double>() : nullptr;
+    job.lower = clouds ? nullptr : dc.as<float>();
+    job.npoints = dn.as<int32_t>();
+    job.stride = max_points;
+    job.count = C;
+    job.rc = threshold;
+    job.counts = dk.as<int32_t>();
+    job.pairs = dp.as<float>();
+    job.pair_cap = cap;
+    int st = split ? persistence_split(c, job.clouds, job.lower, dn.as<int32_t>(), npoints, C, max_points, threshold,
+                                       pairs, cap, kk)
+                   : betti_impl(c, job);
     if (!st) {
         if (!split) {
             HIP_TRY(c, hipMemcpy(kk.data(), dk.p, 16 * (size_t)C, hipMemcpyDeviceToHost));

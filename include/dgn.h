@@ -72,7 +72,10 @@ int dgn_ctx_synchronize(dgn_ctx* ctx);
  * DGN_DEBUG_WIDE_WALK    0 = the u16-coded wide complexes' whole apparent phase inside the per-wave
  *                        wide kernel (default 1: the workgroup-per-complex walk pass before it);
  * DGN_DEBUG_SPLIT_CHUNK  > 0: the component split of dgn_host_persistence[_lower] above 2,048 points
- *                        takes at most this many clouds per chunk (its chunk loop on small inputs). */
+ *                        takes at most this many clouds per chunk (its chunk loop on small inputs);
+ * DGN_DEBUG_WALK_SLICE   > 0: a slice of the u16-coded wide list holds at most this many complexes (the
+ *                        multi-slice loop, its second stream and buffer pair on small inputs); 0 = the
+ *                        byte budgets' size. */
 enum {
     DGN_DEBUG_FORCE_RETRY = 1,
     DGN_DEBUG_WIDE_WAVES = 2,
@@ -82,7 +85,8 @@ enum {
     DGN_DEBUG_BIG_LOG2 = 6,
     DGN_DEBUG_EMIT_CHUNK = 7,
     DGN_DEBUG_WIDE_WALK = 8,
-    DGN_DEBUG_SPLIT_CHUNK = 9
+    DGN_DEBUG_SPLIT_CHUNK = 9,
+    DGN_DEBUG_WALK_SLICE = 10
 };
 int dgn_ctx_set_debug(dgn_ctx* ctx, int knob, int value);
 /* Diagnostics: complexes the capacity-retry launches reduced since the last call (synchronizes). */

@@ -181,3 +181,48 @@ def test_walk_pass_matches_per_wave_walk(ctx):
             a1 = np.array(sorted(map(tuple, p1[c, d, :n])))
             assert np.array_equal(a0, a1), (c, d)
     assert np.array_equal(c0, c1) and np.array_equal(f0.view(np.uint64), f1.view(np.uint64))
+
+
+def test_walk_slices_small(ctx):
+    """The u16-coded wide list in several slices (DGN_DEBUG_WALK_SLICE, a test knob): cap 2 gives
+    three slices (the third waits for the first's reductions and reuses its buffers), cap 1 six
+    (each buffer twice), on the second stream with the two walk / code buffers; cap 2 with
+    DGN_DEBUG_WIDE_WALK = 0 three slices on the context stream with one buffer. Counts and emitted
+    pairs equal the uncapped (single-slice) run's."""
+    rng = np.random.default_rng(37)
+    sizes = [362, 65, 129, 200, 257, 330]
+    clouds = np.zeros((len(sizes), max(sizes), 3))
+    for c, n in enumerate(sizes):
+        clouds[c, :n] = rng.integers(0, 7, size=(n, 3)) if c % 2 else rng.uniform(0, 6.5, size=(n, 3))
+    npts = np.array(sizes, dtype=np.int32)
+    p1, k1 = ctx.host_persistence(clouds, npts, 1.9, cap=8192)
+    try:
+        for slice_cap, walk in ((2, 1), (1, 1), (2, 0)):
+            ctx.set_debug(dgn.abi.DEBUG_WALK_SLICE, slice_cap)
+            ctx.set_debug(dgn.abi.DEBUG_WIDE_WALK, walk)
+            p, k = ctx.host_persistence(clouds, npts, 1.9, cap=8192)
+            assert np.array_equal(k, k1), (slice_cap, walk)
+            for c in range(len(sizes)):
+                for d, col in ((0, 0), (1, 2), (2, 3)):
+                    n = k1[c, col]
+                    assert np.array_equal(p[c, d, :n], p1[c, d, :n]), (slice_cap, walk, c, d)
+    finally:
+        ctx.set_debug(dgn.abi.DEBUG_WALK_SLICE, 0)
+        ctx.set_debug(dgn.abi.DEBUG_WIDE_WALK, 1)
+
+
+def test_walk_slices_fcc256_10A(ctx):
+    """One FCC-256 structure at 10 A with the wide list capped at 100 complexes per slice: three
+    equalised slices of at most 86, double-buffered on the second stream. Counts and statistics
+    against the verbatim-Ripser fixture, and byte for byte against the uncapped run."""
+    fx = np.load(os.path.join(GOLDEN, "rc10.npz"))
+    batch = dgn.synth_batch("fcc", 4, 1)
+    f1, c1 = ctx.host_betti(batch, 10.0)
+    ctx.set_debug(dgn.abi.DEBUG_WALK_SLICE, 100)
+    try:
+        f, c = ctx.host_betti(batch, 10.0)
+    finally:
+        ctx.set_debug(dgn.abi.DEBUG_WALK_SLICE, 0)
+    assert np.array_equal(c, fx["fcc256_0/counts"])
+    np.testing.assert_allclose(f, fx["fcc256_0/features"], rtol=FEAT_RTOL, atol=FEAT_ATOL)
+    assert np.array_equal(c, c1) and np.array_equal(f.view(np.uint64), f1.view(np.uint64))
