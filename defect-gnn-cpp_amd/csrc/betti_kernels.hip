@@ -67,15 +67,6 @@ constexpr uint32_t kLazyBit = 0x80000000u;  // vmeta: V = {column simplex} (pack
 constexpr uint8_t kMcNone = 0xFF;     // not a column, or no cofacet
 constexpr uint8_t kMcCleared = 0xFE;  // triangle is the pivot of a dim-1 column (clearing)
 
-// error bits (mirrored in dgn_api.cpp)
-constexpr uint32_t kErrTooManyPoints = 1u << 0;
-constexpr uint32_t kErrWorkCol = 1u << 1;
-constexpr uint32_t kErrNA = 1u << 2;
-constexpr uint32_t kErrPiv = 1u << 3;
-constexpr uint32_t kErrPairs = 1u << 4;
-constexpr uint32_t kErrR = 1u << 5;
-constexpr uint32_t kErrCapacity = kErrWorkCol | kErrNA | kErrPiv | kErrPairs | kErrR;
-
 // scratch layout per wave (bytes)
 struct ScratchLayout {
     static constexpr int64_t na_key = 0;                             // uint64 [kNACap] (unsorted)
@@ -131,15 +122,10 @@ constexpr int betti_waves_per_simd() { return NP <= 48 ? DGN_NARROW_WAVES : 4; }
 // small helpers
 // ---------------------------------------------------------------------------------------
 // One-wave workgroups: a wave's LDS instructions execute in order, so lane-to-lane hand-offs
-// through LDS need only a compiler barrier. __syncthreads() would add a workgroup release
-// fence (s_waitcnt vmcnt(0)) that stalls on every in-flight global load/store; it is kept only
-// where data passes between lanes through global scratch.
-__device__ __forceinline__ void lds_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-// move a wave-uniform value to an SGPR so dependent integer math runs on the scalar unit
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni64(uint64_t x) {
-    return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
-}
+// through LDS need only a compiler barrier (wave_lds_sync, dgn_device.hpp). __syncthreads() would
+// add a workgroup release fence (s_waitcnt vmcnt(0)) that stalls on every in-flight global
+// load/store; it is kept only where data passes between lanes through global scratch.
+//
 // lanes [0, m) as a mask (full EXEC): one v_cmp into an SGPR pair. The narrow kernel is bound by
 // the scalar unit's issue rate (one SALU per SIMD every ~4 cycles against a VALU every ~2.4 at 8
 // waves per SIMD, tools/ubench/issue.hip), so masks and per-entry arithmetic go to the VALU where
@@ -147,7 +133,6 @@ __device__ __forceinline__ uint64_t uni64(uint64_t x) {
 __device__ __forceinline__ uint64_t lanes_below(int m) {
     return __builtin_amdgcn_ballot_w64((int)(threadIdx.x & 63) < m);
 }
-__device__ __forceinline__ int c2(int x) { return x * (x - 1) / 2; }
 __device__ __forceinline__ int c3(int x) { return x * (x - 1) * (x - 2) / 6; }
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, kWave);
@@ -430,13 +415,6 @@ struct Complex {
         return dim == 1 ? dlowb((x >> 8) & 255, x & 255) : tri_diamb((x >> 16) & 255, (x >> 8) & 255, x & 255);
     }
 
-    // Pivot of the column sum(delta s, s in V) (whole wave): the F-minimal cofacet of odd
-    // multiplicity, restricted to keys above `floor` (the column's previous pivot: adding the
-    // owner column cancels it and every other entry of both columns is larger). Lane k
-    // evaluates the cofacet s u {k} of every s in V; one cofacet tau arises once per facet of
-    // tau in V, always in a different lane (k = tau \ s), so the multiplicity of the wave
-    // minimum is the popcount of a ballot. Even multiplicity: raise the floor and repeat.
-    // kInf for the zero column.
     // key of the cofacet s u {k} for lane k (k < n); its high word is kNoCode (above every real
     // key) if k is not a common neighbour of s: the LDS matrix holds kNoCode for distances above
     // thr and on the diagonal, so the diameter maximum carries it. The low word, ~packed(tau), is
@@ -570,7 +548,7 @@ struct Complex {
     // initial pivot, all computed lane-parallel; larger sets are rank-sorted into scratch.
     __device__ void reduce_serial(int dim, int nna) {
         const int lane = lane_id();
-        if (nna > kNACap) { err |= kErrNA; return; }
+        if (nna > kNACap) { err |= kBErrNA; return; }
         const uint64_t* gk = sp<uint64_t>(ScratchLayout::na_key);
         const uint64_t* gt = sp<uint64_t>(ScratchLayout::na_tau);
         const bool regs = nna <= 2 * kWave;
@@ -673,13 +651,13 @@ struct Complex {
                             }
                         }
                     }
-                    if (!ok) { err |= kErrWorkCol; return; }
+                    if (!ok) { err |= kBErrWorkCol; return; }
                     tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);
                     if (tau == kInf) break;  // zero column: essential class, not emitted
                     owner = (int)uni((uint32_t)find_pivot(npiv, tau));
                     app = uni(owner >= 0 ? kNone : apparent_owner_wave(dim, tau));
                     if (owner < 0 && app == kNone) break;  // tau is this column's pivot
-                    if (++guard > 100000) { err |= kErrWorkCol; return; }
+                    if (++guard > 100000) { err |= kBErrWorkCol; return; }
                 }
                 if (tau == kInf) continue;  // zero column
             }
@@ -697,12 +675,12 @@ struct Complex {
                 const uint32_t tp = key_packed(tau);
                 set_cleared((tp >> 16) & 255, (tp >> 8) & 255, tp & 255);
             }
-            if (npiv >= kPivCap) { err |= kErrPiv; return; }
+            if (npiv >= kPivCap) { err |= kBErrPiv; return; }
             uint32_t meta;
             if (v == 0) {
                 meta = kLazyBit | cp;
             } else {
-                if (vused + v > kVStoreCap || v > 511) { err |= kErrR; return; }
+                if (vused + v > kVStoreCap || v > 511) { err |= kBErrR; return; }
                 for (int t = lane; t < v; t += kWave) {
                     const uint32_t x = t < kWave ? vs0 : vs1;
                     at(gvstore, vused + t) = x;
@@ -712,9 +690,182 @@ struct Complex {
             }
             piv_push(npiv, tau, meta);
             npiv = (int)uni((uint32_t)(npiv + 1));
-            lds_sync();
+            wave_lds_sync();
         }
     }
+
+    // ---- the phases of one complex (whole wave), in betti_kernel's order. Each takes the lane
+    // index from its own lane_id(), which is opaque to the compiler: it cannot hoist lane-derived
+    // masks and per-lane addresses out of the complex loop, where they were live across the whole
+    // kernel and spilled (16 VGPRs at the 96-VGPR budget of NP = 44)
+
+    // adjacency (sparse_distance_matrix: i != j and d <= thr, ripser.cpp:386-395) into s.adj;
+    // returns this lane's row
+    __device__ __forceinline__ uint64_t build_adjacency() {
+        const int lane = lane_id();
+        uint64_t myadj = 0;
+        for (int i = 0; i < n; ++i) {
+            // the kNoCode diagonal fails the test: no self loops
+            const uint64_t row = ballot(s.D[i * S + lane] != kNoCode) & lanes_below(n);
+            myadj = lane == i ? row : myadj;
+        }
+        if (lane < NP) s.adj[lane] = myadj;  // (lanes >= NP would write past adj)
+        return myadj;
+    }
+
+    // dim 0: Prim on F-keys == Kruskal's forest in Ripser order (ripser.cpp:725-762).
+    // best = the lane's F-minimal edge to the forest (kInf once the lane is in the forest, and for
+    // lanes >= n); the wave minimum of its high word (the diameter) alone decides unless two lanes
+    // tie on it. Deaths and forest parents stay in registers (lane t: death t; each lane its own
+    // parent) and are written once after the loop.
+    __device__ __forceinline__ void spanning_forest(uint64_t myadj) {
+        const int lane = lane_id();
+        bool in_tree = lane == 0, root = lane == 0;
+        int parent = 0;
+        uint32_t death = 0;  // rank code
+        uint64_t best = kInf;
+        if (lane < n && lane != 0 && (myadj & 1ull)) best = ekey(0, lane);
+        if (n >= 1) n_inf0 = 1;
+        uint64_t tree = 1;  // forest vertices (uniform)
+        for (int added = 1; added < n; ++added) {
+            const uint32_t hi = (uint32_t)(best >> 32);
+            const uint32_t mh = wave_min_u32(hi);
+            int v;
+            bool newcomp = false;
+            if (mh == 0xFFFFFFFFu) {  // new component: lowest vertex outside the forest
+                v = __ffsll((unsigned long long)(~tree & lanes_below(n))) - 1;
+                n_inf0 += 1;
+                newcomp = true;
+            } else {
+                uint64_t bal = ballot(hi == mh);
+                if (__popcll(bal) > 1) {  // equal diameters: the low words (F-order index) decide
+                    const uint32_t ml = wave_min_u32(hi == mh ? (uint32_t)best : 0xFFFFFFFFu);
+                    bal = ballot(best == (((uint64_t)mh << 32) | ml));
+                }
+                v = __ffsll((unsigned long long)bal) - 1;
+                if (mh != zero_code) {  // (0, d) emitted only if d != 0 (ripser.cpp:741-748)
+                    death = lane == n_d0 ? mh : death;
+                    n_d0 += 1;
+                }
+            }
+            tree |= 1ull << v;
+            if (lane == v) {
+                in_tree = true;
+                root = newcomp;
+                best = kInf;
+            }
+            if (!in_tree && ((myadj >> v) & 1ull)) {
+                const uint64_t k = ekey(v, lane);
+                if (k < best) { best = k; parent = v; }
+            }
+        }
+        if (lane < n_d0) at(sp<uint32_t>(ScratchLayout::d0), lane) = death;  // codes; f32 after decode_outputs
+        if (lane < NP) s.par[lane] = (lane < n && !root) ? (uint8_t)parent : (uint8_t)0xFF;
+        wave_lds_sync();
+    }
+
+    // edge list (i > j, d <= thr), row-major; returns the number of edges
+    __device__ __forceinline__ int edge_list() {
+        const int lane = lane_id();
+        uint16_t* edges = sp<uint16_t>(ScratchLayout::edges);
+        const uint64_t low = lane < n ? (s.adj[lane] & ((lane == 0) ? 0ull : ((1ull << lane) - 1ull))) : 0ull;
+        const int c = __popcll(low);
+        const int inc = wave_inclusive_sum(c);
+        // readlane, not a shuffle: the count must be a scalar (a shuffle result is a
+        // vector value to the compiler, and every loop over the edges would be exec-masked)
+        const int n_edges = (int)uni((uint32_t)__builtin_amdgcn_readlane(inc, kWave - 1));
+        int off = inc - c;
+        uint64_t mm = low;
+        while (mm) {
+            const int j = __ffsll((unsigned long long)mm) - 1;
+            mm &= mm - 1;
+            at(edges, off++) = (uint16_t)((lane << 8) | j);
+        }
+        __syncthreads();  // edge list (global scratch) visible to every lane
+        return n_edges;
+    }
+
+    // The shared tail of an apparent-pass round (whole wave): the lanes with na_col append their
+    // column (key, initial pivot) to the non-apparent list, the lanes with dfr their packed column
+    // to the deferred list; both counts advance.
+    __device__ __forceinline__ void append_columns(bool na_col, uint64_t colkey, uint64_t best, bool dfr, uint32_t col,
+                                                   int& nna, int& ndef) {
+        const uint64_t bal = ballot(na_col);
+        if (na_col) {
+            const int slot = nna + mask_prefix(bal);
+            if (slot < kNACap) {
+                at(sp<uint64_t>(ScratchLayout::na_key), slot) = colkey;
+                at(sp<uint64_t>(ScratchLayout::na_tau), slot) = best;
+            }
+        }
+        nna += __popcll(bal);
+        const uint64_t bd = ballot(dfr);
+        if (dfr) at(sp<uint32_t>(ScratchLayout::defer), ndef + mask_prefix(bd)) = col;
+        ndef += __popcll(bd);
+    }
+
+    // one lane per edge column (active lanes: packed edge ed), at most `steps` walk steps
+    __device__ __forceinline__ void edge_col(bool active, uint32_t ed, int steps, int& nna, int& ndef) {
+        bool na_col = false, dfr = false;
+        uint64_t colkey = 0, best = kInf;
+        if (active) {
+            const int i = ed >> 8, j = ed & 255;
+            uint32_t mc = kMcNone;
+            if (!is_tree(i, j)) {
+                const uint32_t dij = dlowb(i, j);
+                colkey = make_key(dij, pack2(i, j));
+                uint64_t cand = s.adj[i] & s.adj[j];
+                if (cand) {
+                    int bk;
+                    bool found;
+                    uint32_t hda, hdb, hdc;
+                    best = min_cofacet_lane(1, i, j, 0, dij, cand, bk, found, hda, hdb, hdc, steps);
+                    dfr = !found && cand != 0;
+                    // apparent iff (i,j) is the F-max facet of its pivot triangle: a
+                    // zero-persistence cofacet whose other facets (bk replacing i or j)
+                    // are shorter, or as long with a larger index (bk above the
+                    // replaced vertex). An apparent pair has zero persistence: no pair
+                    // is emitted (death > birth only, ripser.cpp:1240).
+                    const bool apparent = found && (bk > i || hdb < dij) && (bk > j || hda < dij);
+                    if (apparent) {
+                        const uint32_t tp = key_packed(best);
+                        set_cleared_lane((tp >> 16) & 255, (tp >> 8) & 255, tp & 255);
+                    } else {
+                        na_col = !dfr;
+                    }
+                    mc = (uint32_t)bk;
+                }
+            }
+            if (!dfr) at(sp<uint8_t>(ScratchLayout::mincof_e), edge_dense(i, j)) = (uint8_t)mc;
+        }
+        append_columns(na_col, colkey, best, dfr, ed, nna, ndef);
+    }
+
+    // dim 1, one lane per column (non-tree edge); returns the number of non-apparent columns
+    // (na_key / na_tau). Round A walks at most kAppSteps steps of every column's min-cofacet walk;
+    // columns not settled by then are listed and walked to the end by round B, so a
+    // round-synchronous pass is not paced by its few long walks.
+    __device__ __forceinline__ int apparent_dim1(int n_edges) {
+        const int lane = lane_id();
+        const uint16_t* edges = sp<uint16_t>(ScratchLayout::edges);
+        const uint32_t* defer = sp<uint32_t>(ScratchLayout::defer);
+        int nna = 0, ndef = 0;
+        for (int base = 0; base < n_edges; base += kWave) {
+            const int e = base + lane;
+            edge_col(e < n_edges, e < n_edges ? (uint32_t)at(edges, e) : 0u, kAppSteps, nna, ndef);
+        }
+        if (ndef) {
+            __syncthreads();  // the deferred list (scratch) is read by other lanes
+            const int nd = ndef;
+            for (int base = 0; base < nd; base += kWave) {
+                const int e = base + lane;
+                edge_col(e < nd, e < nd ? at(defer, e) : 0u, 1 << 20, nna, ndef);
+            }
+        }
+        __syncthreads();
+        return nna;
+    }
+
 };
 
 
@@ -847,13 +998,13 @@ __device__ __forceinline__ uint32_t rank_codes(BettiSmem<NP>& s, const float* __
     constexpr int kLdsKeys = NP * S / 4;
     uint64_t* kl = reinterpret_cast<uint64_t*>(s.D);
     const int lane = lane_id();
-    const int tot = c2(n);
+    const int tot = tri_c2(n);
     // (1) compaction of the distances <= thr, t-order; lane l holds entries t = l + 64 u, its
     // (i, j) advanced incrementally (entry t of the packing is row i, column t - c2(i))
     int i = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)lane)) * 0.5f);
-    i -= c2(i) > lane;
-    i += c2(i + 1) <= lane;
-    int j = lane - c2(i);
+    i -= tri_c2(i) > lane;
+    i += tri_c2(i + 1) <= lane;
+    int j = lane - tri_c2(i);
     int m = 0;
     for (int t0 = 0; t0 < tot; t0 += 2 * kWave) {
         const int t = t0 + lane;
@@ -883,17 +1034,17 @@ __device__ __forceinline__ uint32_t rank_codes(BettiSmem<NP>& s, const float* __
     m = (int)uni((uint32_t)m);
     if (m > kRankMax<NP>) return kRankDense;
     if constexpr (kLdsKeys < kRankMax<NP>) __syncthreads();  // scratch keys are read by other lanes
-    lds_sync();
+    wave_lds_sync();
     auto key_at = [&](int e) __attribute__((always_inline)) {
         if constexpr (kLdsKeys >= kRankMax<NP>) return kl[e];
         else return e < kLdsKeys ? kl[e] : at(keys, e);
     };
     // the matrix starts as kNoCode everywhere (pairs above thr, the diagonal)
     auto clear = [&]() __attribute__((always_inline)) {
-        lds_sync();
+        wave_lds_sync();
         uint32_t* Dw = reinterpret_cast<uint32_t*>(s.D);
         for (int w = lane; w < NP * S / 2; w += kWave) Dw[w] = (kNoCode << 16) | kNoCode;
-        lds_sync();
+        wave_lds_sync();
     };
     uint32_t z;
     if constexpr (NP <= 48) {
@@ -902,16 +1053,17 @@ __device__ __forceinline__ uint32_t rank_codes(BettiSmem<NP>& s, const float* __
         z = m <= 512 ? rank_sorted<8>(s.D, S, key_at, clear, m, sv_out, lane)
                      : rank_sorted<16>(s.D, S, key_at, clear, m, sv_out, lane);
     }
-    lds_sync();
+    wave_lds_sync();
     return z;
 }
 
 template <int NP>
 __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kernel(BettiLaunch bl) {
     __shared__ BettiSmem<NP> s;
-    // the lane index is re-derived opaquely at every phase (relane): the compiler cannot hoist
-    // lane-derived masks and per-lane addresses out of the complex loop, where they were live
-    // across the whole kernel and spilled (16 VGPRs at the 96-VGPR budget of NP = 44)
+    // the lane index is re-derived opaquely at every phase (relane here, lane_id() in the phases
+    // that are members of Complex): the compiler cannot hoist lane-derived masks and per-lane
+    // addresses out of the complex loop, where they were live across the whole kernel and spilled
+    // (16 VGPRs at the 96-VGPR budget of NP = 44)
     int lane = lane_id();
     auto relane = [&]() __attribute__((always_inline)) {
         lane = lane_id();
@@ -923,17 +1075,7 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
     // complexes of this launch: all of them, or the overflow list written by the bucket pass
     const int64_t total = bl.work_list ? (int64_t)*bl.work_len : A;
     for (;;) {
-        // Wave-uniform dequeue without a branch on the lane: every lane adds (lane == 0) to the
-        // queue (one atomic after the compiler's wave combine) and lane 0's ticket is read back
-        // with v_readlane into an SGPR, so the loop exit and everything keyed on the complex (gi,
-        // n) are scalar branches. Round 2 handed lane 0's ticket to the wave through an LDS slot
-        // behind `if (lane == 0)`; a `continue` out of the loop then let the compiler thread a copy
-        // of the loop head specialised for lanes 1..63 -- for them the atomic is skipped, so the
-        // copy re-reads the unchanged slot (a `readlane` of the specialised ticket constant-folds
-        // to the same effect) and spins while lane 0 waits in the exit guard: the gfx950 "hang"
-        // (DESIGN.md 3.2).
-        const uint32_t ticket = atomicAdd((unsigned int*)bl.queue, lane == 0 ? 1u : 0u);
-        const int64_t chunk0 = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)ticket, 0) * kChunk;
+        const int64_t chunk0 = (int64_t)wave_ticket(bl.queue, lane) * kChunk;
         if (chunk0 >= total) break;
         for (int64_t wi = chunk0; wi < chunk0 + kChunk && wi < total; ++wi) {
             const int64_t gi = bl.work_list ? (int64_t)(int32_t)uni((uint32_t)bl.work_list[wi]) : wi;
@@ -941,9 +1083,7 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
             double* feat = bl.features ? bl.features + 35 * gi : nullptr;
             if (n > NP) {
                 if (bl.skip_above) continue;  // reduced by the overflow launch
-                if (lane == 0) atomicOr(bl.error_flag, kErrTooManyPoints);
-                if (feat && lane < 35) feat[lane] = __builtin_nan("");
-                if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+                betti_fail_complex(bl, gi, kBErrPoints, lane);
                 continue;
             }
             // 1/count(species) weight (betti_features.cpp:62-63, 77), from the distance pass
@@ -956,8 +1096,6 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
             uint8_t* cscr = scratch;
             asm volatile("" : "+s"(cscr));
             Complex<NP> cx{s, n, bl.thr, cscr, 0u, 0, 0, 0, 0};
-            cx.zero_code = 0xFFFFFFFFu;
-            constexpr int S = BettiSmem<NP>::S;
             cx.zero_code = rank_codes<NP>(s, bl.lower + gi * bl.tri_stride, n, cx.thr,
                                           cx.template sp<float>(ScratchLayout::svals),
                                           cx.template sp<uint64_t>(ScratchLayout::rankk));
@@ -970,171 +1108,33 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
                 } else if (bl.retry_list) {
                     if (lane == 0) bl.retry_list[atomicAdd(bl.retry_len, 1u)] = (int32_t)gi;
                 } else {
-                    if (lane == 0) atomicOr(bl.error_flag, kErrWorkCol);
-                    if (feat && lane < 35) feat[lane] = __builtin_nan("");
-                    if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+                    betti_fail_complex(bl, gi, kBErrWorkCol, lane);
                 }
                 continue;
             }
-            lds_sync();
+            wave_lds_sync();
             // ---- adjacency (sparse_distance_matrix: i != j and d <= thr, ripser.cpp:386-395) ----
             relane();
-            uint64_t myadj = 0;  // this lane's row
-            {
-                for (int i = 0; i < n; ++i) {
-                    // the kNoCode diagonal fails the test: no self loops
-                    const uint64_t row = ballot(s.D[i * S + lane] != kNoCode) & lanes_below(n);
-                    myadj = lane == i ? row : myadj;
-                }
-                if (lane < NP) s.adj[lane] = myadj;  // (lanes >= NP would write past adj)
-            }
+            const uint64_t myadj = cx.build_adjacency();
             uint32_t* d0s = cx.template sp<uint32_t>(ScratchLayout::d0);  // codes; f32 after decode_outputs
             const int dim_max = n - 2 < 2 ? n - 2 : 2;  // ripser.cpp:560
             cx.n_inf0 = 0;
             cx.n_d0 = 0;
-            // ---- dim 0: Prim on F-keys == Kruskal's forest in Ripser order (ripser.cpp:725-762) ----
-            relane();
-            // best = the lane's F-minimal edge to the forest (kInf once the lane is in the forest,
-            // and for lanes >= n); the wave minimum of its high word (the diameter) alone decides
-            // unless two lanes tie on it. Deaths and forest parents stay in registers (lane t: death
-            // t; each lane its own parent) and are written once after the loop.
-            {
-                bool in_tree = lane == 0, root = lane == 0;
-                int parent = 0;
-                uint32_t death = 0;  // rank code
-                uint64_t best = kInf;
-                if (lane < n && lane != 0 && (myadj & 1ull)) best = cx.ekey(0, lane);
-                if (n >= 1) cx.n_inf0 = 1;
-                uint64_t tree = 1;  // forest vertices (uniform)
-                for (int added = 1; added < n; ++added) {
-                    const uint32_t hi = (uint32_t)(best >> 32);
-                    const uint32_t mh = wave_min_u32(hi);
-                    int v;
-                    bool newcomp = false;
-                    if (mh == 0xFFFFFFFFu) {  // new component: lowest vertex outside the forest
-                        v = __ffsll((unsigned long long)(~tree & lanes_below(n))) - 1;
-                        cx.n_inf0 += 1;
-                        newcomp = true;
-                    } else {
-                        uint64_t bal = ballot(hi == mh);
-                        if (__popcll(bal) > 1) {  // equal diameters: the low words (F-order index) decide
-                            const uint32_t ml = wave_min_u32(hi == mh ? (uint32_t)best : 0xFFFFFFFFu);
-                            bal = ballot(best == (((uint64_t)mh << 32) | ml));
-                        }
-                        v = __ffsll((unsigned long long)bal) - 1;
-                        if (mh != cx.zero_code) {  // (0, d) emitted only if d != 0 (ripser.cpp:741-748)
-                            death = lane == cx.n_d0 ? mh : death;
-                            cx.n_d0 += 1;
-                        }
-                    }
-                    tree |= 1ull << v;
-                    if (lane == v) {
-                        in_tree = true;
-                        root = newcomp;
-                        best = kInf;
-                    }
-                    if (!in_tree && ((myadj >> v) & 1ull)) {
-                        const uint64_t k = cx.ekey(v, lane);
-                        if (k < best) { best = k; parent = v; }
-                    }
-                }
-                if (lane < cx.n_d0) at(d0s, lane) = death;
-                if (lane < NP) s.par[lane] = (lane < n && !root) ? (uint8_t)parent : (uint8_t)0xFF;
-            }
-            lds_sync();
+            cx.spanning_forest(myadj);
             // ---- edge list (i > j, d <= thr), row-major ----
             relane();
             uint16_t* edges = cx.template sp<uint16_t>(ScratchLayout::edges);
-            int n_edges = 0;
-            {
-                const uint64_t low = lane < n ? (s.adj[lane] & ((lane == 0) ? 0ull : ((1ull << lane) - 1ull))) : 0ull;
-                const int c = __popcll(low);
-                const int inc = wave_inclusive_sum(c);
-                // readlane, not a shuffle: the count must be a scalar (a shuffle result is a
-                // vector value to the compiler, and every loop over the edges would be exec-masked)
-                n_edges = (int)uni((uint32_t)__builtin_amdgcn_readlane(inc, kWave - 1));
-                int off = inc - c;
-                uint64_t mm = low;
-                while (mm) {
-                    const int j = __ffsll((unsigned long long)mm) - 1;
-                    mm &= mm - 1;
-                    at(edges, off++) = (uint16_t)((lane << 8) | j);
-                }
-            }
-            __syncthreads();  // edge list (global scratch) visible to every lane
+            const int n_edges = cx.edge_list();
             cx.n_p1 = 0;
             cx.n_p2 = 0;
             uint64_t* na_key = cx.template sp<uint64_t>(ScratchLayout::na_key);
             uint64_t* na_tau = cx.template sp<uint64_t>(ScratchLayout::na_tau);
             uint8_t* mincof = cx.template sp<uint8_t>(ScratchLayout::mincof);
-            uint8_t* mincof_e = cx.template sp<uint8_t>(ScratchLayout::mincof_e);
-                    // ---- dim 1: one lane per column (non-tree edge) ----
-                    relane();
+            // ---- dim 1: one lane per column (non-tree edge) ----
+            relane();
             uint32_t* defer = cx.template sp<uint32_t>(ScratchLayout::defer);
             if (dim_max >= 1) {
-                int nna = 0, ndef = 0;
-                // One lane per edge column. Round A walks at most kAppSteps steps of every column's
-                // min-cofacet walk; columns not settled by then are listed and walked to the end by
-                // round B, so a round-synchronous pass is not paced by its few long walks.
-                auto edge_col = [&](bool active, uint32_t ed, int steps) {
-                    bool na_col = false, dfr = false;
-                    uint64_t colkey = 0, best = kInf;
-                    if (active) {
-                        const int i = ed >> 8, j = ed & 255;
-                        uint32_t mc = kMcNone;
-                        if (!cx.is_tree(i, j)) {
-                            const uint32_t dij = cx.dlowb(i, j);
-                            colkey = make_key(dij, pack2(i, j));
-                            uint64_t cand = s.adj[i] & s.adj[j];
-                            if (cand) {
-                                int bk;
-                                bool found;
-                                uint32_t hda, hdb, hdc;
-                                best = cx.min_cofacet_lane(1, i, j, 0, dij, cand, bk, found, hda, hdb, hdc, steps);
-                                dfr = !found && cand != 0;
-                                // apparent iff (i,j) is the F-max facet of its pivot triangle: a
-                                // zero-persistence cofacet whose other facets (bk replacing i or j)
-                                // are shorter, or as long with a larger index (bk above the
-                                // replaced vertex). An apparent pair has zero persistence: no pair
-                                // is emitted (death > birth only, ripser.cpp:1240).
-                                const bool apparent = found && (bk > i || hdb < dij) && (bk > j || hda < dij);
-                                if (apparent) {
-                                    const uint32_t tp = key_packed(best);
-                                    cx.set_cleared_lane((tp >> 16) & 255, (tp >> 8) & 255, tp & 255);
-                                } else {
-                                    na_col = !dfr;
-                                }
-                                mc = (uint32_t)bk;
-                            }
-                        }
-                        if (!dfr) at(mincof_e, edge_dense(i, j)) = (uint8_t)mc;
-                    }
-                    const uint64_t bal = ballot(na_col);
-                    if (na_col) {
-                        const int slot = nna + mask_prefix(bal);
-                        if (slot < kNACap) {
-                            at(na_key, slot) = colkey;
-                            at(na_tau, slot) = best;
-                        }
-                    }
-                    nna += __popcll(bal);
-                    const uint64_t bd = ballot(dfr);
-                    if (dfr) at(defer, ndef + mask_prefix(bd)) = ed;
-                    ndef += __popcll(bd);
-                };
-                for (int base = 0; base < n_edges; base += kWave) {
-                    const int e = base + lane;
-                    edge_col(e < n_edges, e < n_edges ? (uint32_t)at(edges, e) : 0u, kAppSteps);
-                }
-                if (ndef) {
-                    __syncthreads();  // the deferred list (scratch) is read by other lanes
-                    const int nd = ndef;
-                    for (int base = 0; base < nd; base += kWave) {
-                        const int e = base + lane;
-                        edge_col(e < nd, e < nd ? at(defer, e) : 0u, 1 << 20);
-                    }
-                }
-                __syncthreads();
+                const int nna = cx.apparent_dim1(n_edges);
                 cx.reduce_serial(1, nna);
                 __syncthreads();  // clearing marks (scratch stores) complete before the dim-2 pass
             }
@@ -1272,19 +1272,17 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
                 }
                 __syncthreads();
                 cx.reduce_serial(2, nna);
-                lds_sync();
+                wave_lds_sync();
             }
             __syncthreads();
-            if (cx.n_p1 > kPairCap || cx.n_p2 > kPairCap) cx.err |= kErrPairs;
+            if (cx.n_p1 > kPairCap || cx.n_p2 > kPairCap) cx.err |= kBErrPairs;
             const uint32_t err = uni(cx.err);
-            if (err && bl.retry_list && (err & kErrCapacity) == err) {
+            if (err && bl.retry_list && (err & kBErrCapacity) == err) {
                 // workspace overflow: the capacity-retry launch (betti_wide_kernel, big layout)
                 // reduces this complex again and writes its outputs
                 if (lane == 0) bl.retry_list[atomicAdd(bl.retry_len, 1u)] = (int32_t)gi;
             } else if (err) {
-                if (lane == 0) atomicOr(bl.error_flag, err);
-                if (feat && lane < 35) at(feat, lane) = __builtin_nan("");
-                if (bl.counts && lane < 4) at(bl.counts + 4 * gi, lane) = -1;
+                betti_fail_complex(bl, gi, err, lane);
             } else {
                 // ---- statistics (betti_features.cpp:24-55, 87-98; utils/math.hpp:9-28) ----
                 relane();
@@ -1301,7 +1299,7 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
                 if (bl.counts && lane < 4)  // #dim0 finite, #dim0 infinite, #dim1, #dim2
                     at(bl.counts + 4 * gi, lane) = lane == 0 ? cx.n_d0 : (lane == 1 ? cx.n_inf0 : (lane == 2 ? cx.n_p1 : cx.n_p2));
             }
-            lds_sync();
+            wave_lds_sync();
         }
     }
 }

@@ -43,10 +43,6 @@ constexpr uint16_t kMcClearedW = 0xFFFE;  // triangle is the pivot of a dim-1 co
 constexpr uint64_t kLazyW = 1ull << 63;    // pivot meta: V = {column simplex} (packed, low bits)
 constexpr uint64_t kNoMetaW = ~0ull;       // pivot not in the table
 constexpr int kMetaLenBits = 24;           // pivot meta: (V-store offset << 24) | V length
-// error bits (decoded in dgn_api.cpp)
-constexpr uint32_t kEPoints = 1u << 0, kEWork = 1u << 1, kENA = 1u << 2, kEPiv = 1u << 3, kEPairs = 1u << 4,
-                   kER = 1u << 5, kEGuard = 1u << 7;
-constexpr uint32_t kECapacity = kEWork | kENA | kEPiv | kEPairs | kER | kEGuard;
 
 __device__ __forceinline__ uint64_t bin2(uint64_t v) { return v * (v - 1) / 2; }
 __device__ __forceinline__ uint64_t bin3(uint64_t v) { return v * (v - 1) * (v - 2) / 6; }
@@ -57,20 +53,11 @@ __device__ __forceinline__ uint64_t rlw64(uint64_t x, int l) {
 }
 // lanes 0 .. m - 1 (m in 0..64)
 __device__ __forceinline__ uint64_t lanes_below_w(int m) { return m >= 64 ? ~0ull : (1ull << m) - 1ull; }
-__device__ __forceinline__ uint32_t uniw(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uniw64(uint64_t x) {
-    return ((uint64_t)uniw((uint32_t)(x >> 32)) << 32) | uniw((uint32_t)x);
-}
-__device__ __forceinline__ void wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 // lane-to-lane hand-off through this wave's global scratch (V list, pivot table, V store, lists):
 // a workgroup-scope fence, which waits for every outstanding memory access of the wave
 // (vmcnt(0) lgkmcnt(0)) without a barrier -- the two waves of a workgroup run different phases
 // of different complexes (betti_wide_body)
 __device__ __forceinline__ void wave_scratch_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-
-// combinatorial index of a packed simplex with nv vertices
-// insert vertex x (not in p) into a packed simplex of nv vertices
-__device__ __forceinline__ int c2i(int x) { return x * (x - 1) / 2; }
 
 // KW: bitset words per vertex the instantiation handles (complexes of up to 64 KW points).
 // BIG (complexes of 513..1024 points): vertices packed in 10 bits, distances replaced by their
@@ -110,8 +97,8 @@ struct WideCx {
         else return rlw(x, l);
     }
     __device__ static PT unip(PT x) {
-        if constexpr (HUGE) return uniw64(x);
-        else return uniw(x);
+        if constexpr (HUGE) return uni64(x);
+        else return uni(x);
     }
     __device__ static int pv(uint64_t p, int field) { return (int)((p >> (VB * field)) & VM); }
     __device__ static uint64_t pidx(int nv, uint64_t p) {
@@ -208,7 +195,7 @@ struct WideCx {
         if constexpr (PRE) {  // the walk pass built the matrix and the threshold code
             (void)gi;
             (void)lane;
-            thrc = uniw(bl.walk.meta[8 * slot + kWmThr]);
+            thrc = uni(bl.walk.meta[8 * slot + kWmThr]);
             return;
         }
         const float* L = bl.lower + gi * bl.tri_stride;
@@ -222,14 +209,14 @@ struct WideCx {
         }
         uint32_t tmax = 0;
         if constexpr (HUGE) wave_scratch_sync();  // the zeroed bitsets (scratch) before the atomics
-        else wave_lds_order();
+        else wave_lds_sync();
         for (int i = 1; i < n; ++i) {
             for (int j0 = 0; j0 < i; j0 += kWave) {
                 const int j = j0 + lane;
                 bool e = false;
                 if (j < i) {
-                    const float v = L[c2i(i) + j];
-                    uint32_t dv = CODED ? Lc[c2i(i) + j] : __float_as_uint(v);
+                    const float v = L[tri_c2(i) + j];
+                    uint32_t dv = CODED ? Lc[tri_c2(i) + j] : __float_as_uint(v);
                     if (GIANT) dv = min(dv, kGiantCodeMax);  // the codes above thr saturate
                     if (MODE == kC16) {
                         D16[(int64_t)i * n + j] = (uint16_t)dv;
@@ -250,7 +237,7 @@ struct WideCx {
             }
         }
         thrc = ~wave_min_u32(~tmax);
-        if (GIANT && thrc >= kGiantCodeMax) err |= kEPoints;  // 2^20 or more distances within thr
+        if (GIANT && thrc >= kGiantCodeMax) err |= kBErrPoints;  // 2^20 or more distances within thr
         // HUGE: the bitsets were built by L2 atomics; the agent-scope fence drops the CU's L1 copies
         if constexpr (HUGE) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
         wave_scratch_sync();
@@ -273,7 +260,7 @@ struct WideCx {
             bp[t] = 0;
             if (t < W && v < n && v != 0 && ((aw(0, t) >> lane) & 1ull)) best[t] = wkey(d(0, v), bin2(v));
         }
-        wave_lds_order();
+        wave_lds_sync();
         n_inf0 = 1;
         n_d0 = 0;
         for (int added = 1; added < n; ++added) {
@@ -307,7 +294,7 @@ struct WideCx {
                 if (lane == 0) par[v] = (uint16_t)u;
             }
             if (lane == (v & 63)) intree |= MT(1) << (v >> 6);
-            wave_lds_order();
+            wave_lds_sync();
 #pragma unroll
             for (int t = 0; t < kWW; ++t) {
                 const int w = 64 * t + lane;
@@ -320,7 +307,7 @@ struct WideCx {
                 }
             }
         }
-        wave_lds_order();
+        wave_lds_sync();
     }
 
     // ---- edges (i > j, d <= thr) in index order ----
@@ -330,7 +317,7 @@ struct WideCx {
         int off = 0;
         for (int i = 1; i < n; ++i)
             for (int w = 0; 64 * w < i; ++w) {
-                uint64_t bits = uniw64(aw(i, w));  // one LDS word: uniform (scalar count below)
+                uint64_t bits = uni64(aw(i, w));  // one LDS word: uniform (scalar count below)
                 const int lim = i - 64 * w;
                 if (lim < 64) bits &= (1ull << lim) - 1ull;
                 if ((bits >> lane) & 1ull) edges[off + mask_prefix(bits)] = pack_edge(i, 64 * w + lane);
@@ -552,7 +539,7 @@ struct WideCx {
                         cb = (int)(ed & VM);
                         cw = 0;
                     }
-                    uint64_t mm = uniw64(aw(ca, cw) & aw(cb, cw));
+                    uint64_t mm = uni64(aw(ca, cw) & aw(cb, cw));
                     const int lim = cb - 64 * cw;
                     if (lim < 64) mm &= (1ull << lim) - 1ull;
                     cm = mm;
@@ -750,7 +737,7 @@ struct WideCx {
             const uint64_t hit = ballot(x == k), emp = ballot(x == 0ull);
             const int fh = hit ? __ffsll((unsigned long long)hit) - 1 : kWave;
             const int fe = emp ? __ffsll((unsigned long long)emp) - 1 : kWave;
-            if (fh < fe) return uniw64(HM[(base + (uint32_t)(probe + fh)) & mask]);
+            if (fh < fe) return uni64(HM[(base + (uint32_t)(probe + fh)) & mask]);
             if (fe < kWave) return kNoMetaW;
         }
         return kNoMetaW;
@@ -900,7 +887,7 @@ struct WideCx {
         }
         const uint16_t m = dim == 1 ? at(mce, (uint32_t)pidx(2, bestf))
                                      : at(sp<uint16_t>(ly.mc_t), (uint32_t)pidx(3, bestf));
-        if (uniw(m) == (uint32_t)vd) app = (PT)bestf;
+        if (uni(m) == (uint32_t)vd) app = (PT)bestf;
         return kNoMetaW;
     }
 
@@ -1093,7 +1080,7 @@ struct WideCx {
     __device__ void reduce(int dim, int nna, int base) {
         const int lane = lane_id();
         if (base + pow2ceil(nna) > ly.na_cap) {
-            err |= kENA;
+            err |= kBErrNA;
             return;
         }
         nna = sort_na(base, nna, dim == 2);
@@ -1115,9 +1102,9 @@ struct WideCx {
             nC = Cc[0];
         }
         for (int ci = 0; ci < nna && err == 0u; ++ci) {
-            const uint64_t colkey = uniw64(nK);
-            uint64_t tau = uniw64(nT);
-            uint64_t tv = uniw64(nV);
+            const uint64_t colkey = uni64(nK);
+            uint64_t tau = uni64(nT);
+            uint64_t tv = uni64(nV);
             const PT cp = unip(nC);
             if (ci + 1 < nna) {
                 nK = K[ci + 1];
@@ -1150,7 +1137,7 @@ struct WideCx {
                         }
                     }
                     if (!ok) {
-                        err |= kEWork;
+                        err |= kBErrWorkCol;
                         break;
                     }
                     tau = v > 0 ? pivot_of_V(dim, v, tau, tv) : kInfW;
@@ -1158,7 +1145,7 @@ struct WideCx {
                     meta = lookup(dim, tau, tv, app, fslot);
                     if (meta == kNoMetaW && app == kNoneP) break;  // tau is this column's pivot
                     if (++guard > ly.guard) {
-                        err |= kEGuard;
+                        err |= kBErrGuard;
                         break;
                     }
                 }
@@ -1183,7 +1170,7 @@ struct WideCx {
                 m = kLazyW | cp;
             } else {
                 if ((int64_t)vused + v > ly.vs_cap) {
-                    err |= kER;
+                    err |= kBErrR;
                     break;
                 }
                 if (!VREG || vspill) {
@@ -1196,7 +1183,7 @@ struct WideCx {
                 vused += v;
             }
             if (!hinsert(tau, m, npiv, fslot)) {
-                err |= kEPiv;
+                err |= kBErrPiv;
                 break;
             }
             ++npiv;
@@ -1218,17 +1205,15 @@ struct WideCx {
     __device__ bool finish(int64_t gi, double weight) {
         const int lane = lane_id();
         double* feat = bl.features ? bl.features + 35 * gi : nullptr;
-        if (n_p1 > ly.p_cap || n_p2 > ly.p_cap) err |= kEPairs;
-        if (err && bl.retry_list && (err & kECapacity) == err) {
+        if (n_p1 > ly.p_cap || n_p2 > ly.p_cap) err |= kBErrPairs;
+        if (err && bl.retry_list && (err & kBErrCapacity) == err) {
             // workspace overflow: listed for the capacity-retry launch (betti_wide_layout big),
             // which writes this complex's outputs
             if (lane == 0) bl.retry_list[atomicAdd(bl.retry_len, 1u)] = (int32_t)gi;
             return false;
         }
         if (err) {
-            if (lane == 0) atomicOr(bl.error_flag, err);
-            if (feat && lane < 35) feat[lane] = __builtin_nan("");
-            if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+            betti_fail_complex(bl, gi, err, lane);
             return false;
         }
         const float* d0s = d0p;
@@ -1277,11 +1262,11 @@ struct WideCx {
         const int lane = lane_id();
         const WalkOut& wo = bl.walk;
         const uint32_t* meta = wo.meta + 8 * slot;
-        n_d0 = (int)uniw(meta[kWmD0]);
-        n_inf0 = (int)uniw(meta[kWmInf0]);
-        const int n1 = (int)uniw(meta[kWmNa1]), ncw = (int)uniw(meta[kWmCl]), nw = (int)uniw(meta[kWmNa2]);
+        n_d0 = (int)uni(meta[kWmD0]);
+        n_inf0 = (int)uni(meta[kWmInf0]);
+        const int n1 = (int)uni(meta[kWmNa1]), ncw = (int)uni(meta[kWmCl]), nw = (int)uni(meta[kWmNa2]);
         if (n1 > wo.cap1 || ncw > wo.cap1 || nw > wo.cap || pow2ceil(n1) + pow2ceil(nw) > ly.na_cap) {
-            err |= kENA;  // a list that overflowed: capacity retry
+            err |= kBErrNA;  // a list that overflowed: capacity retry
             return;
         }
         const uint32_t* CL = wo.cl + slot * (int64_t)wo.cap1;
@@ -1342,8 +1327,8 @@ struct WideCx {
             for (int i = lane_id(); i < ncl && i < ly.na_cap; i += kWave) clbits()[cl[i] >> 5] = 0u;
         } else if constexpr (PRE) {
             // every set bit of the bitmap is listed (a word shared by two entries is zeroed twice)
-            const int64_t words = ((int64_t)c2i(n) * (n - 2) / 3 + 31) / 32 + 1;
-            const int ncw = (int)uniw(bl.walk.meta[8 * wslot + kWmCl]);
+            const int64_t words = ((int64_t)tri_c2(n) * (n - 2) / 3 + 31) / 32 + 1;
+            const int ncw = (int)uni(bl.walk.meta[8 * wslot + kWmCl]);
             if (ncl > ly.na_cap || ncw > bl.walk.cap1) {
                 for (int64_t i = lane_id(); i < words; i += kWave) at(clbits(), (uint32_t)i) = 0u;
             } else {
@@ -1386,19 +1371,14 @@ __device__ __forceinline__ void betti_wide_body(const BettiLaunch& bl, const Wid
     uint16_t* par = reinterpret_cast<uint16_t*>(kHugeMode ? lds : lds + ly.nmax * ww);
     const int64_t total = (int64_t)*bl.wide_len;
     for (;;) {
-        // wave-uniform dequeue without a branch on the lane (see betti_kernels.hip): every lane adds
-        // (lane == 0), lane 0's ticket goes to an SGPR
-        const uint32_t ticket = atomicAdd(bl.wide_queue, lane == 0 ? 1u : 0u);
-        const int64_t wi = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)ticket, 0);
+        const int64_t wi = (int64_t)wave_ticket(bl.wide_queue, lane);
         if (wi >= total) break;
-        const int64_t gi = (int64_t)(int32_t)uniw((uint32_t)bl.wide_list[wi]);
-        const int n = (int)uniw((uint32_t)bl.npoints[gi]);
+        const int64_t gi = (int64_t)(int32_t)uni((uint32_t)bl.wide_list[wi]);
+        const int n = (int)uni((uint32_t)bl.npoints[gi]);
         // complexes above kWideRegular points never reach the regular launch (the bucket pass lists
         // them for the rank-coded retry launch); a larger one here is outside the layout
         if (n > ly.nmax) {
-            if (lane == 0) atomicOr(bl.error_flag, kEPoints);
-            if (bl.features && lane < 35) bl.features[35 * gi + lane] = __builtin_nan("");
-            if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+            betti_fail_complex(bl, gi, kBErrPoints, lane);
         } else {
             WideCx<KW, MODE, PRE> cx{bl, ly, adj, par, scr, n, (n + 63) / 64, bl.thr, 0u, 0, 0, 0, 0};
             if (MODE != kF32) cx.vals = bl.rank_sorted + wi * bl.rank_stride;
@@ -1444,15 +1424,12 @@ __device__ __forceinline__ void betti_reduce_body(const BettiLaunch& bl, const W
     uint8_t* scr = ly.base + slot * ly.total;
     const int64_t total = (int64_t)*bl.wide_len;
     for (;;) {
-        const uint32_t ticket = atomicAdd(bl.wide_queue, lane == 0 ? 1u : 0u);  // as betti_wide_body
-        const int64_t wi = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)ticket, 0);
+        const int64_t wi = (int64_t)wave_ticket(bl.wide_queue, lane);
         if (wi >= total) break;
-        const int64_t gi = (int64_t)(int32_t)uniw((uint32_t)bl.wide_list[wi]);
-        const int n = (int)uniw((uint32_t)bl.npoints[gi]);
+        const int64_t gi = (int64_t)(int32_t)uni((uint32_t)bl.wide_list[wi]);
+        const int n = (int)uni((uint32_t)bl.npoints[gi]);
         if (n > ly.nmax) {
-            if (lane == 0) atomicOr(bl.error_flag, kEPoints);
-            if (bl.features && lane < 35) bl.features[35 * gi + lane] = __builtin_nan("");
-            if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+            betti_fail_complex(bl, gi, kBErrPoints, lane);
             continue;
         }
         WideCx<KW, kC16, true> cx{bl, ly, nullptr, nullptr, scr, n, (n + 63) / 64, bl.thr, 0u, 0, 0, 0, 0};
@@ -1498,10 +1475,6 @@ constexpr int kWalkWaves = 16;
 #endif
 constexpr int kWalkRing = 128;  // queued triangles per wave (refilled below 64: at most 63 + 64 held)
 __device__ __forceinline__ uint32_t c2u(int x) { return ((uint32_t)x * (uint32_t)(x - 1)) >> 1; }
-__device__ __forceinline__ uint32_t walk_ticket(uint32_t* ctr) {  // wave-uniform, no branch on the lane
-    const uint32_t t = atomicAdd(ctr, lane_id() == 0 ? 1u : 0u);
-    return (uint32_t)__builtin_amdgcn_readlane((int)t, 0);
-}
 // LDS counters of the walk pass
 enum { kWcWalk = 0, kWcN2 = 1, kWcTmax = 2, kWcRow = 3, kWcN1 = 4, kWcCl = 5, kWcD0 = 6, kWcInf0 = 7 };
 // append the lanes with `p` to a per-complex list whose length is LDS counter *ctr (one LDS atomic
@@ -1545,7 +1518,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
         const uint32_t* Lc = bl.rank_codes + wi * bl.rank_stride;
         uint32_t tmax = 0;
         for (int i = 1 + wv; i < n; i += kWalkWaves) {
-            const int ci = c2i(i);
+            const int ci = tri_c2(i);
             for (int j0 = 0; j0 < i; j0 += kWave) {
                 const int j = j0 + lane;
                 bool e = false;
@@ -1583,12 +1556,12 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
             const int v = 64 * t + lane;
             best[t] = kInfW;
             bp[t] = 0;
-            if (t < W && v < n && v != 0 && ((aw(0, t) >> lane) & 1ull)) best[t] = H::wkey(T[c2i(v)], bin2(v));
+            if (t < W && v < n && v != 0 && ((aw(0, t) >> lane) & 1ull)) best[t] = H::wkey(T[tri_c2(v)], bin2(v));
         }
         // a death's value is 0 iff its code is 0 and the complex's smallest distance is 0 (codes are
         // first indices of value runs in the sorted triangle)
         const bool zero0 = __uint_as_float(vals[0]) == 0.0f;
-        wave_lds_order();
+        wave_lds_sync();
         int nd0 = 0, ninf = 1;
         for (int added = 1; added < n; ++added) {
             uint64_t lmin = kInfW;
@@ -1621,13 +1594,13 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                 if (lane == 0) par[v] = (uint16_t)u;
             }
             if (lane == (v & 63)) intree |= 1u << (v >> 6);
-            wave_lds_order();
-            const int cv = c2i(v);
+            wave_lds_sync();
+            const int cv = tri_c2(v);
 #pragma unroll
             for (int t = 0; t < KWM; ++t) {
                 const int x = 64 * t + lane;
                 if (t < W && x < n && !((intree >> t) & 1u) && ((aw(v, t) >> lane) & 1ull)) {
-                    const uint64_t k = H::wkey(dd(v, cv, x, c2i(x)), v > x ? bin2(v) + x : bin2(x) + v);
+                    const uint64_t k = H::wkey(dd(v, cv, x, tri_c2(x)), v > x ? bin2(v) + x : bin2(x) + v);
                     if (k < best[t]) {
                         best[t] = k;
                         bp[t] = v;
@@ -1635,7 +1608,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                 }
             }
         }
-        wave_lds_order();
+        wave_lds_sync();
         float* d0s = wo.d0 + wi * wo.d0stride;
         for (int i = lane; i < nd0; i += kWave) d0s[i] = __uint_as_float(vals[d0c[i]]);
         if (lane == 0) {
@@ -1646,9 +1619,9 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
         uint16_t* D = wo.dmat + wi * wo.dstride;
         const int ns = (n + 3) & ~3;  // 8-byte rows (the reductions read them as packed vectors)
         for (int i = wv - 1; i < n; i += kWalkWaves - 1) {
-            const int ci = c2i(i);
+            const int ci = tri_c2(i);
             for (int x = lane; x < ns; x += kWave)
-                D[i * ns + x] = x == i || x >= n ? (uint16_t)0xFFFF : (x < i ? T[ci + x] : T[c2i(x) + i]);
+                D[i * ns + x] = x == i || x >= n ? (uint16_t)0xFFFF : (x < i ? T[ci + x] : T[tri_c2(x) + i]);
         }
     }
     __syncthreads();  // the forest (is a dim-1 column a tree edge?)
@@ -1662,11 +1635,11 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
         uint64_t* oe1 = wo.e1 + wi * (int64_t)wo.cap1;
         uint32_t* ocl = wo.cl + wi * (int64_t)wo.cap1;
         for (;;) {
-            const int i = 1 + (int)walk_ticket(&ctr[kWcRow]);
+            const int i = 1 + (int)wave_ticket(&ctr[kWcRow], lane_id());
             if (i >= n) break;
-            const int ci = c2i(i);
+            const int ci = tri_c2(i);
             for (int w0 = 0; 64 * w0 < i; ++w0) {
-                uint64_t bits = uniw64(aw(i, w0));
+                uint64_t bits = uni64(aw(i, w0));
                 const int lim = i - 64 * w0;
                 if (lim < 64) bits &= (1ull << lim) - 1ull;
                 if (!bits) continue;
@@ -1678,7 +1651,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                     uint16_t mc = kMcNoneW;
                     if (!(par[i] == j || par[j] == i)) {
                         const uint32_t dij = T[ci + j];
-                        const int cj = c2i(j);
+                        const int cj = tri_c2(j);
                         int bk = -1;
                         bool found = false;
                         uint32_t bdd = 0xFFFFFFFFu, hda = 0, hdb = 0;
@@ -1688,7 +1661,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                                 const int bit = 63 - __clzll((long long)m);
                                 m &= ~(1ull << bit);
                                 const int k = 64 * w + bit;
-                                const int ck = c2i(k);
+                                const int ck = tri_c2(k);
                                 const uint32_t da = dd(i, ci, k, ck), db = dd(j, cj, k, ck);
                                 const uint32_t dk = max(da, db);
                                 if (dk <= dij) {
@@ -1750,14 +1723,14 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                         if (ca >= 0 && 64 * (bw + 1) < ca) {
                             ++bw;
                         } else {
-                            ca = n - 1 - (int)walk_ticket(&ctr[kWcWalk]);
+                            ca = n - 1 - (int)wave_ticket(&ctr[kWcWalk], lane_id());
                             if (ca < 2) {
                                 exhausted = true;
                                 break;
                             }
                             bw = 0;
                         }
-                        uint64_t r = uniw64(aw(ca, bw));
+                        uint64_t r = uni64(aw(ca, bw));
                         const int lim = ca - 64 * bw;
                         if (lim < 64) r &= (1ull << lim) - 1ull;
                         bm = r;
@@ -1767,7 +1740,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                     bm &= bm - 1ull;
                     cw = 0;
                 }
-                mm = uniw64(aw(ca, cw) & aw(cb, cw));
+                mm = uni64(aw(ca, cw) & aw(cb, cw));
                 const int lim = cb - 64 * cw;
                 if (lim < 64) mm &= (1ull << lim) - 1ull;
                 if (mm) break;
@@ -1778,7 +1751,7 @@ __global__ __launch_bounds__(kWave * kWalkWaves) void betti_walk_kernel(BettiLau
                     ((uint32_t)ca << 18) | ((uint32_t)cb << 9) | (uint32_t)(64 * cw + lane);
             tail += __popcll(mm);
         }
-        wave_lds_order();
+        wave_lds_sync();
         {  // idle lanes take queued triangles, in order
             const uint64_t need = ballot(!act);
             const int avail = tail - head;

@@ -280,8 +280,7 @@ int take_betti_flag(dgn_ctx* c) {
     HIP_TRY(c, hipMemsetAsync(c->bflags.p, 0, 2 * sizeof(uint32_t), c->stream));
     if (g)
         return fail(c, DGN_ERR_INTERNAL, "Betti neighbour search disagreed with the count pass (flags " + std::to_string(g) + ")");
-    if (f & 1u) return fail(c, DGN_ERR_UNSUPPORTED, "local complex exceeds the kernel's point envelope");
-    if (f & 64u) return fail(c, DGN_ERR_INTERNAL, "reduction order check failed");
+    if (f & kBErrPoints) return fail(c, DGN_ERR_UNSUPPORTED, "local complex exceeds the kernel's point envelope");
     return fail(c, DGN_ERR_CAPACITY, "per-complex workspace overflow, flags " + std::to_string(f));
 }
 

@@ -62,6 +62,26 @@ __device__ __forceinline__ int mask_prefix(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// move a wave-uniform value to an SGPR so dependent integer math runs on the scalar unit
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ int32_t uni(int32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t uni64(uint64_t x) {
+    return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
+}
+
+// Wave-uniform ticket from a work counter without a branch on the lane: every lane adds
+// (lane == 0) to the counter (one atomic after the compiler's wave combine) and lane 0's ticket is
+// read back with v_readlane into an SGPR, so the loop exit and everything keyed on the ticket are
+// scalar branches. Round 2 handed lane 0's ticket to the wave through an LDS slot behind
+// `if (lane == 0)`; a `continue` out of the loop then let the compiler thread a copy of the loop
+// head specialised for lanes 1..63 -- for them the atomic is skipped, so the copy re-reads the
+// unchanged slot (a `readlane` of the specialised ticket constant-folds to the same effect) and
+// spins while lane 0 waits in the exit guard: the gfx950 "hang" (DESIGN.md 3.2).
+__device__ __forceinline__ uint32_t wave_ticket(uint32_t* counter, int lane) {
+    const uint32_t t = atomicAdd(counter, lane == 0 ? 1u : 0u);
+    return (uint32_t)__builtin_amdgcn_readlane((int)t, 0);
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll

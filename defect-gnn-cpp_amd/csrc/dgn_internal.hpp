@@ -25,6 +25,19 @@ constexpr uint32_t kGErrMismatch = 1u << 1;  // emit / Betti search disagrees wi
 constexpr uint32_t kGErrFar = 1u << 2;       // a position more than 500 cells away from the origin
 constexpr uint32_t kGErrMissedHit = 1u << 3; // a count-pass hit failed the emit's exact test
 
+// Betti reduction error bits (BettiLaunch::error_flag), set by the narrow and the wide kernels and
+// decoded by take_betti_flag (dgn_api.cpp); its messages print the number
+constexpr uint32_t kBErrPoints = 1u << 0;   // more points than the kernel's envelope
+constexpr uint32_t kBErrWorkCol = 1u << 1;  // working column (V list) overflow, or more rank keys than the sort holds
+constexpr uint32_t kBErrNA = 1u << 2;       // non-apparent column list overflow
+constexpr uint32_t kBErrPiv = 1u << 3;      // pivot table overflow
+constexpr uint32_t kBErrPairs = 1u << 4;    // pair list overflow
+constexpr uint32_t kBErrR = 1u << 5;        // V store overflow
+                                            // bit 6: reserved (no kernel sets it)
+constexpr uint32_t kBErrGuard = 1u << 7;    // a column's reduction ran past the step guard (wide kernel)
+// errors the capacity-retry launch can cure with a larger workspace
+constexpr uint32_t kBErrCapacity = kBErrWorkCol | kBErrNA | kBErrPiv | kBErrPairs | kBErrR | kBErrGuard;
+
 struct GraphLaunch {
     const StructMeta* meta;
     const int32_t* atom_struct;  // [A] structure of each atom (prep_structures_kernel)
@@ -173,6 +186,12 @@ struct BettiLaunch {
     int64_t rank_stride;
     WalkOut walk;                // u16-coded wide launch after the walk pass (walk.meta null: none)
 };
+// a complex no launch will reduce (whole wave): its error bits, NaN features and -1 counts
+__device__ __forceinline__ void betti_fail_complex(const BettiLaunch& bl, int64_t gi, uint32_t err, int lane) {
+    if (lane == 0) atomicOr(bl.error_flag, err);
+    if (bl.features && lane < 35) bl.features[35 * gi + lane] = __builtin_nan("");
+    if (bl.counts && lane < 4) bl.counts[4 * gi + lane] = -1;
+}
 // wide complexes (65..kWideMaxPoints points, betti_wide.hip): per-wave scratch layout. Up to
 // kWideRegular points in the regular launch; above it (rank-coded: 10-bit vertices up to
 // kWideBigPoints, 11-bit vertices and the adjacency in scratch above) in the retry launch after

@@ -32,8 +32,6 @@ namespace dgn {
 
 constexpr int kW = kGraphBlock / kWave;  // waves per block
 
-__device__ __forceinline__ int32_t uni_i32(int32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-
 // fractional coordinates u = p . R (R = inverse lattice), one fixed operation order everywhere
 __device__ __forceinline__ double frac_k(const double* R, int k, double x, double y, double z) {
     return (x * R[k] + y * R[3 + k]) + z * R[6 + k];
@@ -325,8 +323,8 @@ __device__ __forceinline__ void for_block_atoms(const GraphLaunch& g, const Stag
     const int64_t g0 = a_begin + tile * qa;
     const int64_t g1 = g0 + qa < a_end ? g0 + qa : a_end;
     if (g0 >= g1) return;
-    const int32_t b_first = uni_i32(g.atom_struct[g0]);
-    const int32_t b_last = uni_i32(g.atom_struct[g1 - 1]);
+    const int32_t b_first = uni(g.atom_struct[g0]);
+    const int32_t b_last = uni(g.atom_struct[g1 - 1]);
     for (int32_t b = b_first; b <= b_last; ++b) {
         const StructMeta M = load_meta_uniform(g.meta + b);
         const int64_t first = M.first;
@@ -1080,7 +1078,7 @@ __global__ __launch_bounds__(kGraphBlock) __attribute__((amdgpu_waves_per_eu(DGN
     // every structure of the tile staged and one-image or few-image? (wave-uniform: metadata in
     // SGPRs)
     bool one = true, all_one = true;
-    for (int32_t b = uni_i32(g.atom_struct[g0]), bl = uni_i32(g.atom_struct[g1 - 1]); b <= bl && one; ++b) {
+    for (int32_t b = uni(g.atom_struct[g0]), bl = uni(g.atom_struct[g1 - 1]); b <= bl && one; ++b) {
         const StructMeta M = load_meta_uniform(g.meta + b);
         one = M.natoms == 0 || ((M.one || M.few) && M.natoms <= kStage);
         all_one = all_one && (M.natoms == 0 || M.one);
@@ -1289,7 +1287,7 @@ __global__ __launch_bounds__(kScanThreads) void block_scan_kernel(int64_t* __res
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int rank_small(const DGN_LDS double* kd, const DGN_LDS uint64_t* kj, int m,
                                           DGN_LDS uint8_t* claim) {
-    m = uni_i32(m);
+    m = uni(m);
     const int lane = lane_id();
     const bool act = lane < m;
     const double me = act ? kd[lane] : 0.0;

@@ -290,3 +290,33 @@ def test_unbounded_threshold(ctx, thr):
     for c in range(len(sizes)):  # the emitted pairs (entries past each count are not written)
         for di, col in ((0, 0), (1, 2), (2, 3)):
             assert np.array_equal(pairs2[c, di, :counts[c, col]], pairs[c, di, :counts[c, col]]), (c, di)
+
+
+def test_wave_slot_reuse_small_clouds(ctx):
+    """Three times as many complexes as the narrow launch has resident waves, so most waves reduce
+    a second and a third complex in the same scratch slot: the min-cofacet marks, the triangle
+    entries and the pivot tables a complex leaves behind must not reach the next one. Small
+    clouds (1..40 points, the 48-point instantiation), half of them on a 3x3x3 grid (exact ties,
+    duplicate points); pairs bit-exact vs the oracle."""
+    rng = np.random.default_rng(17)
+    C, maxp, thr, cap = 24576, 40, 1.5, 64
+    npts = rng.integers(1, 41, size=C)
+    npts[::7] = 3
+    npts[::11] = 1
+    npts[::13] = 2
+    npts = npts.astype(np.int32)
+    clouds = np.zeros((C, maxp, 3))
+    for c in range(C):
+        n = npts[c]
+        clouds[c, :n] = rng.integers(0, 3, size=(n, 3)) if c % 2 == 0 else rng.uniform(0, 3.0, size=(n, 3))
+    refs = [O.persistence(O.local_distances(clouds[c, :npts[c]]), npts[c], np.float32(thr)) for c in range(C)]
+    assert max(len(r[d]) for r in refs for d in ("dim0", "dim1", "dim2")) <= cap  # the cap hides nothing
+    pairs, counts = ctx.host_persistence(clouds, npts, thr, cap=cap)
+    bad = []
+    for c, r in enumerate(refs):
+        ok = counts[c, 1] == r["n_inf0"] and all(
+            np.array_equal(pairs[c, di, :counts[c, [0, 2, 3][di]]], r[d]) for di, d in enumerate(("dim0", "dim1", "dim2")))
+        if not ok:
+            bad.append((c, int(npts[c]), counts[c].tolist(), [len(r[d]) for d in ("dim0", "dim1", "dim2")], r["n_inf0"]))
+    assert not bad, (len(bad), bad[:10])
+    assert np.all(counts[npts == 1] == [0, 1, 0, 0])

@@ -18,7 +18,7 @@ MARKS = [
     ("                    tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);\n", "PIV", False),
     ("                    tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);\n", "AFTER_PIV", True),
     ("            // ---- tau is the pivot of this column ----\n", "FINAL", True),
-    ("            npiv = (int)uni((uint32_t)(npiv + 1));\n            lds_sync();\n", "FINAL_END", True),
+    ("            npiv = (int)uni((uint32_t)(npiv + 1));\n            wave_lds_sync();\n", "FINAL_END", True),
 ]
 
 
