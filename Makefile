@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall 
 LIB      := $(PKG)/lib/libdgn.so
 
 KOBJS := $(BUILD)/graph_kernels.o $(BUILD)/betti_kernels.o $(BUILD)/betti_wide.o $(BUILD)/betti_rank.o \
-         $(BUILD)/betti_split.o $(BUILD)/node_kernels.o $(BUILD)/dgn_api.o
+         $(BUILD)/betti_split.o $(BUILD)/node_kernels.o $(BUILD)/pca_kernels.o $(BUILD)/pca_host.o $(BUILD)/dgn_api.o
 
 all: $(LIB) facade oracle
 
@@ -46,6 +46,11 @@ $(BUILD)/dgn_api.o: $(CSRC)/dgn_api.cpp include/dgn.h $(CSRC)/dgn_internal.hpp $
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
+# host-only part of the PCA fit (merge, eigen-solve): no HIP, the plain C++ compiler
+$(BUILD)/pca_host.o: $(CSRC)/pca_host.cpp include/dgn.h
+	@mkdir -p $(BUILD)
+	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c $< -o $@
+
 $(LIB): $(KOBJS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KOBJS)
@@ -60,7 +65,8 @@ clean:
 .PHONY: all oracle clean facade
 
 # Host-code sanitizer run (ASan + UBSan) over the CPU oracle and the facade's host-only code
-# (parser, Structure, PCA): builds build_san/san_check and runs it on the POSCAR fixtures.
+# (parser, Structure, PCA) and the library's host-only PCA merge / solve (csrc/pca_host.cpp): builds
+# build_san/san_check and runs it on the POSCAR fixtures.
 SAN      := $(PKG)/build_san
 SANFLAGS := -O1 -g -std=c++17 -fno-omit-frame-pointer -ffp-contract=off -fsanitize=address,undefined \
             -fno-sanitize-recover=undefined -Iinclude -I$(FDIR)/include -Ioracle
@@ -68,8 +74,8 @@ sanitize: $(SAN)/san_check
 	mkdir -p $(SAN)/tmp
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $(SAN)/san_check tests/golden/poscar $(SAN)/tmp
 $(SAN)/san_check: $(FDIR)/tools/san_check.cpp oracle/oracle.cpp oracle/oracle.h $(FDIR)/src/vasp_parser.cpp \
-                  $(FDIR)/src/structure.cpp $(FDIR)/src/pca.cpp $(FHDRS)
+                  $(FDIR)/src/structure.cpp $(FDIR)/src/pca.cpp $(CSRC)/pca_host.cpp $(FHDRS)
 	@mkdir -p $(SAN)
 	$(CXX) $(SANFLAGS) -o $@ $(FDIR)/tools/san_check.cpp oracle/oracle.cpp $(FDIR)/src/vasp_parser.cpp \
-	    $(FDIR)/src/structure.cpp $(FDIR)/src/pca.cpp
+	    $(FDIR)/src/structure.cpp $(FDIR)/src/pca.cpp $(CSRC)/pca_host.cpp
 .PHONY: sanitize

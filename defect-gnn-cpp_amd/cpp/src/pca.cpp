@@ -101,6 +101,26 @@ void PCA::fit(const dgn::MatrixXd& x, int n_components) {
     fitted_ = true;
 }
 
+void PCA::fit_moments(const dgn_pca_moments& m, int n_components) {
+    const int d = BETTI_FEATURE_DIM;
+    if (n_components < 0 || n_components > d) throw std::invalid_argument("PCA: bad n_components");
+    if (m.n < 2) throw std::runtime_error("PCA::fit_moments: fewer than two rows accumulated");
+    std::vector<double> mean(static_cast<size_t>(d)), comp(static_cast<size_t>(d * n_components)),
+        ratio(static_cast<size_t>(n_components));
+    if (dgn_pca_solve(&m, n_components, mean.data(), comp.data(), ratio.data()) != DGN_OK)
+        throw std::runtime_error("PCA::fit_moments: dgn_pca_solve rejected the moments");
+    mean_.resize(d);
+    for (int k = 0; k < d; ++k) mean_[k] = mean[static_cast<size_t>(k)];
+    components_.resize(d, n_components);
+    explained_var_.resize(n_components);
+    for (int c = 0; c < n_components; ++c) {
+        for (int k = 0; k < d; ++k) components_(k, c) = comp[static_cast<size_t>(k * n_components + c)];
+        explained_var_[c] = ratio[static_cast<size_t>(c)];
+    }
+    n_components_ = n_components;
+    fitted_ = true;
+}
+
 dgn::MatrixXd PCA::transform(const dgn::MatrixXd& x) const {
     if (!fitted_) throw std::runtime_error("PCA::transform called before fit() or load()");
     if (x.cols() != mean_.size()) throw std::runtime_error("PCA::transform: column count mismatch");

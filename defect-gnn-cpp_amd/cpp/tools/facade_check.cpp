@@ -3,6 +3,7 @@
 //   facade_check <poscar> <r_cutoff> <max_neighbors> <out.txt>   (GPU: graph, Betti, persistence)
 //   facade_check parse <poscar> <out.txt>                           (host: POSCAR -> Structure)
 //   facade_check pca <features.bin> <n_components> <out.txt>        (host: load_betti_features + PCA)
+//   facade_check pca_dev <features.bin> <n_components> <out.txt>    (GPU: the same through PCA::fit_device)
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -56,10 +57,11 @@ static int host_modes(int argc, char** argv) {
         std::fclose(f);
         return 0;
     }
-    if (mode == "pca" && argc == 5) {
+    if ((mode == "pca" || mode == "pca_dev") && argc == 5) {
         const dgn::MatrixXd x = topology::load_betti_features(argv[2]);
         topology::PCA pca;
-        const dgn::MatrixXd t = pca.fit_transform(x, std::stoi(argv[3]));
+        if (mode == "pca_dev") pca.fit_device(x, std::stoi(argv[3]));
+        const dgn::MatrixXd t = mode == "pca_dev" ? pca.transform(x) : pca.fit_transform(x, std::stoi(argv[3]));
         const std::string model = std::string(argv[4]) + ".pca_model.bin";
         pca.save(model);
         topology::PCA back;
@@ -116,7 +118,8 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    if (argc >= 2 && (std::string(argv[1]) == "parse" || std::string(argv[1]) == "pca")) {
+    if (argc >= 2 && (std::string(argv[1]) == "parse" || std::string(argv[1]) == "pca" ||
+                      std::string(argv[1]) == "pca_dev")) {
         try {
             const int rc = host_modes(argc, argv);
             if (rc >= 0) return rc;

@@ -1,5 +1,5 @@
 // preprocess_betti — batch driver equivalent to reference src/preprocess/preprocess_betti.cpp:30-143.
-//   preprocess_betti [--resume] [raw_path processed_path [r_cutoff [n_pca_components [batch_structures]]]]
+//   preprocess_betti [--resume] [--stream-pca] [raw_path processed_path [r_cutoff [n_pca_components [batch_structures]]]]
 // Scans raw_path/*.vasp, orders ids "X_Y" by (X, Y) (:21-28,43-46), computes the N x 35 Betti
 // features of every structure, writes processed_path/betti/<id>.bin (save_betti_features format),
 // fits the PCA over all atoms and writes processed_path/pca_model.bin. Structures are sent to the
@@ -7,6 +7,9 @@
 // --resume: a structure whose betti/<id>.bin already exists (and matches its POSCAR's atom count) is
 // loaded (load_betti_features) instead of parsed and recomputed, and its file is left untouched, as the Python upstream skips existing outputs
 // (.reference_code/Defect_GNN/Betti_number.py:208-209); the PCA is still fitted over every atom.
+// --stream-pca: every batch's features (computed or loaded) are reduced on the GPU into one
+// dgn_pca_moments as they arrive (dgn_host_pca_accumulate) and pca_model.bin is written from
+// PCA::fit_moments: no feature matrix outlives its batch and no N x 35 matrix is built.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "crystal/structure.hpp"
+#include "dgn/runtime.hpp"
 #include "io/vasp_parser.hpp"
 #include "topology/betti_features.hpp"
 #include "topology/pca.hpp"
@@ -56,10 +60,11 @@ int main(int argc_in, char** argv_in) {
     double r_cutoff = 10;
     int n_pca = 6;
     size_t batch = 1024;
-    bool resume = false;
+    bool resume = false, stream_pca = false;
     std::vector<char*> args;
     for (int i = 0; i < argc_in; ++i) {
         if (i > 0 && std::string(argv_in[i]) == "--resume") resume = true;
+        else if (i > 0 && std::string(argv_in[i]) == "--stream-pca") stream_pca = true;
         else args.push_back(argv_in[i]);
     }
     const int argc = static_cast<int>(args.size());
@@ -85,6 +90,9 @@ int main(int argc_in, char** argv_in) {
 
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<dgn::MatrixXd> all;
+        dgn_pca_moments moments;  // --stream-pca: every atom's features so far
+        dgn_pca_moments_init(&moments);
+        std::vector<double> rows;  // --stream-pca: one batch's features, rows contiguous
         size_t total_atoms = 0;
         size_t skipped = 0;
         for (size_t lo = 0; lo < ids.size(); lo += batch) {
@@ -137,9 +145,23 @@ int main(int argc_in, char** argv_in) {
                     feats[todo[t] - lo] = std::move(got[t]);
                 }
             }
+            if (stream_pca) rows.clear();
             for (size_t i = lo; i < hi; ++i) {
-                total_atoms += static_cast<size_t>(feats[i - lo].rows());
-                all.push_back(std::move(feats[i - lo]));
+                const dgn::MatrixXd& f = feats[i - lo];
+                total_atoms += static_cast<size_t>(f.rows());
+                if (!stream_pca) {
+                    all.push_back(std::move(feats[i - lo]));
+                    continue;
+                }
+                for (std::ptrdiff_t r = 0; r < f.rows(); ++r)
+                    for (std::ptrdiff_t k = 0; k < f.cols(); ++k) rows.push_back(f(r, k));
+            }
+            if (stream_pca && !rows.empty()) {
+                auto& rt = dgn::runtime();
+                std::lock_guard<std::mutex> lk(rt.mu);
+                dgn::check(dgn_host_pca_accumulate(rt.ctx, rows.data(),
+                                                   static_cast<int64_t>(rows.size() / topology::BETTI_FEATURE_DIM), &moments),
+                           "preprocess_betti --stream-pca");
             }
             log("[" + std::to_string(hi) + "/" + std::to_string(ids.size()) + "] structures done");
         }
@@ -148,6 +170,20 @@ int main(int argc_in, char** argv_in) {
         log("Betti features: " + std::to_string(ids.size()) + " structures, " + std::to_string(total_atoms) +
             " atoms in " + std::to_string(secs) + " s");
 
+        if (stream_pca) {
+            if (moments.skipped > 0)
+                log("PCA: " + std::to_string(moments.skipped) + " atoms with non-finite features left out");
+            if (moments.n > 1) {
+                topology::PCA pca;
+                pca.fit_moments(moments, n_pca);
+                pca.save(processed_path + "/pca_model.bin");
+                double ratio = 0;
+                for (std::ptrdiff_t k = 0; k < pca.explained_variance_ratio().size(); ++k) ratio += pca.explained_variance_ratio()[k];
+                log("PCA explained variance ratio: " + std::to_string(ratio));
+            }
+            log("done");
+            return 0;
+        }
         dgn::MatrixXd stacked(static_cast<std::ptrdiff_t>(total_atoms), topology::BETTI_FEATURE_DIM);
         std::ptrdiff_t row = 0;
         for (const auto& f : all)

@@ -1,6 +1,7 @@
 // san_check: host-code sanitizer driver (`make sanitize`, ASan + UBSan). Exercises the CPU
 // oracle (test infrastructure) and the facade's host-only code paths (POSCAR parser, Structure,
-// PCA fit/transform/save/load) on the committed fixtures and synthetic inputs; GPU entry points
+// PCA fit/transform/save/load, and the library's host-only PCA moments merge / solve of
+// csrc/pca_host.cpp) on the committed fixtures and synthetic inputs; GPU entry points
 // are not called (no device in the build container). Exit status 0 = clean run.
 //   san_check <poscar_dir> <tmp_dir>
 #include <cmath>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "crystal/structure.hpp"
+#include "dgn.h"
 #include "io/vasp_parser.hpp"
 #include "oracle.h"
 #include "topology/pca.hpp"
@@ -42,6 +44,59 @@ static int check_structure_oracle(const crystal::Structure& s, double rc) {
     if (oracle_structure_betti(lat.data(), pos.data(), sp.data(), n, rc, feat.data(), cnt.data()) != 0) return 1;
     for (double f : feat)
         if (!std::isfinite(f)) return 2;
+    return 0;
+}
+
+// moments of rows [lo, hi) of x, as PCA::fit computes them
+static dgn_pca_moments host_moments(const dgn::MatrixXd& x, int lo, int hi) {
+    dgn_pca_moments m;
+    dgn_pca_moments_init(&m);
+    m.n = hi - lo;
+    for (int a = 0; a < 35 && hi > lo; ++a) {
+        for (int i = lo; i < hi; ++i) m.mean[a] += x(i, a);
+        m.mean[a] /= static_cast<double>(hi - lo);
+    }
+    for (int a = 0; a < 35; ++a)
+        for (int b = 0; b < 35; ++b)
+            for (int i = lo; i < hi; ++i) m.m2[a * 35 + b] += (x(i, a) - m.mean[a]) * (x(i, b) - m.mean[b]);
+    return m;
+}
+
+// dgn_pca_moments_merge / dgn_pca_solve: two halves against the whole, n = 0 on either side,
+// k = 0 and k = 35, the rejected arguments, and PCA::fit_moments against PCA::fit
+static int check_pca_moments(const dgn::MatrixXd& x, const topology::PCA& fitted) {
+    const int n = static_cast<int>(x.rows());
+    const dgn_pca_moments whole = host_moments(x, 0, n);
+    dgn_pca_moments ab = host_moments(x, 0, n / 3);
+    const dgn_pca_moments b = host_moments(x, n / 3, n), empty = host_moments(x, 0, 0);
+    if (dgn_pca_moments_merge(&ab, &b) != DGN_OK || ab.n != whole.n) return 1;
+    for (int a = 0; a < 35; ++a)
+        if (std::fabs(ab.mean[a] - whole.mean[a]) > 1e-12 * (1 + std::fabs(whole.mean[a]))) return 2;
+    for (int e = 0; e < 35 * 35; ++e)
+        if (std::fabs(ab.m2[e] - whole.m2[e]) > 1e-9 * (1 + std::fabs(whole.m2[e]))) return 3;
+    dgn_pca_moments left = empty, right = whole;
+    if (dgn_pca_moments_merge(&left, &whole) != DGN_OK || dgn_pca_moments_merge(&right, &empty) != DGN_OK) return 4;
+    for (int e = 0; e < 35 * 35; ++e)
+        if (left.m2[e] != whole.m2[e] || right.m2[e] != whole.m2[e]) return 5;
+    if (left.n != whole.n || right.n != whole.n) return 5;
+    std::vector<double> mean(35), comp(35 * 35), ratio(35);
+    if (dgn_pca_solve(&whole, 0, mean.data(), nullptr, nullptr) != DGN_OK) return 6;
+    if (dgn_pca_solve(&whole, 35, mean.data(), comp.data(), ratio.data()) != DGN_OK) return 7;
+    double sum = 0;
+    for (double r : ratio) sum += r;
+    if (std::fabs(sum - 1.0) > 1e-12) return 8;
+    if (dgn_pca_solve(&whole, 36, mean.data(), comp.data(), ratio.data()) != DGN_ERR_ARG ||
+        dgn_pca_solve(&whole, -1, mean.data(), comp.data(), ratio.data()) != DGN_ERR_ARG ||
+        dgn_pca_solve(&empty, 6, mean.data(), comp.data(), ratio.data()) != DGN_ERR_ARG ||
+        dgn_pca_moments_merge(&left, &left) != DGN_ERR_ARG)
+        return 9;
+    topology::PCA p;
+    p.fit_moments(ab, 6);
+    for (int c = 0; c < 6; ++c) {
+        if (std::fabs(p.explained_variance_ratio()[c] - fitted.explained_variance_ratio()[c]) > 1e-9) return 10;
+        for (int a = 0; a < 35; ++a)
+            if (std::fabs(p.components()(a, c) - fitted.components()(a, c)) > 1e-8) return 11;
+    }
     return 0;
 }
 
@@ -88,6 +143,10 @@ int main(int argc, char** argv) {
     for (int i = 0; i < y.rows(); ++i)
         for (int j = 0; j < y.cols(); ++j)
             if (std::fabs(y(i, j) - z(i, j)) > 1e-9) bad |= 8;
+    if (const int st = check_pca_moments(x, p)) {
+        std::fprintf(stderr, "san_check: PCA moments check %d failed\n", st);
+        bad |= 16;
+    }
     std::printf("san_check %s\n", bad ? "FAILED" : "ok");
     return bad;
 }

@@ -106,6 +106,7 @@ struct HostScalars {
     uint32_t emit_flag;  // copied asynchronously after every graph emit
     uint32_t pad;
     uint32_t betti_flags[2];  // copied asynchronously after every Betti pass: search, reduction bits
+    double pca[kPcaResult];   // dgn_dev_pca_accumulate: n, mean[35], scatter upper triangle[630]
 };
 
 // sticky device words of the Betti pass (context lifetime; never cleared by a count pass): the
@@ -156,6 +157,8 @@ struct dgn_ctx {
     int dbg_walk_slice = 0;        // complexes per slice of the u16-coded wide list (0 = its byte budgets)
     int dbg_big_log2 = 0;          // capacity-retry layout's first-level table size log2 (0 = natural 24)
     int dbg_emit_chunk = 0;        // tiles per launch of the large-row emit (0 = the byte budget's)
+    int dbg_pca_chunk = 0;         // rows per staged chunk of dgn_host_pca_accumulate (0 = kPcaHostChunkRows)
+    DevBuf pca_work, pca_stage;    // PCA moments: tile partials + result; the host entry point's staged rows
     // host staging
     DevBuf h_lat, h_pos, h_spec, h_off;
     DevBuf dist_scratch;  // emit distance rows when the caller wants an RBF but no distances
@@ -1029,6 +1032,43 @@ inline uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// One block's moments on the stream (two passes, each with its fixed-order partial sum), read back
+// (the one wait) and merged into *m on the host. rows > 0.
+constexpr int64_t kPcaHostChunkRows = 262144;  // dgn_host_pca_accumulate: 73 MB of staged rows
+int pca_accumulate_impl(dgn_ctx* c, const double* betti_dev, int64_t rows, dgn_pca_moments* m) {
+    HIP_TRY(c, c->pca_work.ensure(sizeof(double) * pca_workspace_doubles(rows)));
+    double* ws = c->pca_work.as<double>();
+    const double R = (double)rows, T = (double)pca_tiles(rows);
+    {   // reads the block once, writes and re-reads 36 words per tile; one add per value
+        TimedLaunch t(c, "pca_sums", R * 8 * kPcaDim + T * 2 * 8 * kPcaSumWidth, R * kPcaDim);
+        HIP_TRY(c, launch_pca_sums(c->stream, betti_dev, rows, ws));
+    }
+    {   // reads the block again, writes and re-reads 630 words per tile; 35 subtractions and the 45
+        // lane tiles' 720 FMAs per row (630 of them the upper triangle, the rest padding and the
+        // diagonal tiles' lower halves)
+        TimedLaunch t(c, "pca_scatter", R * 8 * kPcaDim + T * 2 * 8 * kPcaTri, R * (kPcaDim + 2.0 * 720));
+        HIP_TRY(c, launch_pca_scatter(c->stream, betti_dev, rows, ws));
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->host->pca, ws + (size_t)pca_tiles(rows) * (kPcaSumWidth + kPcaTri),
+                              sizeof(double) * kPcaResult, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, stream_sync(c));
+    const double* r = c->host->pca;
+    dgn_pca_moments part;
+    dgn_pca_moments_init(&part);
+    part.n = (int64_t)r[0];
+    part.skipped = rows - part.n;
+    if (part.n < 0 || part.n > rows) return fail(c, DGN_ERR_INTERNAL, "dgn_pca_accumulate: row count out of range");
+    if (part.n > 0) {
+        for (int a = 0; a < kPcaDim; ++a) part.mean[a] = r[1 + a];
+        const double* u = r + 1 + kPcaDim;
+        for (int a = 0; a < kPcaDim; ++a)
+            for (int b = a; b < kPcaDim; ++b) part.m2[a * kPcaDim + b] = part.m2[b * kPcaDim + a] = *u++;
+    }
+    if (dgn_pca_moments_merge(m, &part) != DGN_OK)
+        return fail(c, DGN_ERR_ARG, "dgn_pca_accumulate: *m holds negative counts");
+    return DGN_OK;
+}
+
 }  // namespace
 
 // ======================================= C ABI ============================================
@@ -1118,6 +1158,7 @@ int dgn_ctx_set_debug(dgn_ctx* c, int knob, int value) {
         case DGN_DEBUG_WIDE_CAP: c->dbg_wide_cap = value > 0 ? value : 0; return DGN_OK;
         case DGN_DEBUG_BIG_LOG2: c->dbg_big_log2 = value > 0 && value < 24 ? value : 0; return DGN_OK;
         case DGN_DEBUG_EMIT_CHUNK: c->dbg_emit_chunk = value > 0 ? value : 0; return DGN_OK;
+        case DGN_DEBUG_PCA_CHUNK: c->dbg_pca_chunk = value > 0 ? value : 0; return DGN_OK;
         default: return fail(c, DGN_ERR_ARG, "dgn_ctx_set_debug: unknown knob " + std::to_string(knob));
     }
 }
@@ -1348,6 +1389,31 @@ int dgn_dev_node_features(dgn_ctx* c, const dgn_batch* b, const double* embed, i
     HIP_TRY(c, stream_sync(c));
     if (c->host->s.error_flag)
         return fail(c, DGN_ERR_ARG, "dgn_dev_node_features: a species key has no embedding row (atom_embeddings.at)");
+    return DGN_OK;
+}
+
+int dgn_dev_pca_accumulate(dgn_ctx* c, const double* betti, int64_t rows, dgn_pca_moments* m) {
+    if (!c || rows < 0 || !m || (rows > 0 && !betti)) return fail(c, DGN_ERR_ARG, "dgn_dev_pca_accumulate: bad args");
+    if (rows == 0) return DGN_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int st = take_emit_flag(c)) return st;
+    return pca_accumulate_impl(c, betti, rows, m);
+}
+
+int dgn_host_pca_accumulate(dgn_ctx* c, const double* betti, int64_t rows, dgn_pca_moments* m) {
+    if (!c || rows < 0 || !m || (rows > 0 && !betti)) return fail(c, DGN_ERR_ARG, "dgn_host_pca_accumulate: bad args");
+    if (rows == 0) return DGN_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int st = take_emit_flag(c)) return st;
+    const int64_t chunk = std::min<int64_t>(rows, c->dbg_pca_chunk > 0 ? c->dbg_pca_chunk : kPcaHostChunkRows);
+    HIP_TRY(c, c->pca_stage.ensure(sizeof(double) * kPcaDim * (size_t)chunk));
+    for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+        const int64_t cnt = std::min(chunk, rows - r0);
+        // the previous chunk's kernels are done: its accumulate waited for the stream
+        HIP_TRY(c, hipMemcpyAsync(c->pca_stage.p, betti + r0 * kPcaDim, sizeof(double) * kPcaDim * (size_t)cnt,
+                                  hipMemcpyHostToDevice, c->stream));
+        if (int st = pca_accumulate_impl(c, c->pca_stage.as<double>(), cnt, m)) return st;
+    }
     return DGN_OK;
 }
 

@@ -308,4 +308,25 @@ hipError_t launch_edge_arrays(hipStream_t s, const int64_t* row_ptr, const int64
                               const int32_t* col, const double* dist, const double* disp, int32_t* src, int32_t* tgt,
                               float* dist32, float* disp32);
 
+// ---- PCA moments of a Betti block (pca_kernels.hip) ----
+// rows are split into tiles of kPcaTileRows (independent of the device: the summation order, and so
+// every bit of the result, depends on the row count alone); one block per tile per pass
+constexpr int kPcaDim = 35;
+constexpr int kPcaTri = kPcaDim * (kPcaDim + 1) / 2;  // 630 upper-triangle entries, row-major, a <= b
+constexpr int kPcaTileRows = 1024;                     // mirrored as dgn.abi.PCA_TILE_ROWS
+constexpr int kPcaSumWidth = kPcaDim + 1;              // pass-1 partial: 35 column sums, finite-row count
+constexpr int kPcaResult = 1 + kPcaDim + kPcaTri;      // n, mean[35], upper[630]
+inline int64_t pca_tiles(int64_t rows) { return (rows + kPcaTileRows - 1) / kPcaTileRows; }
+// doubles of workspace for `rows` rows: [tiles][36] pass-1 partials, [tiles][630] pass-2 partials,
+// then the kPcaResult result words
+inline size_t pca_workspace_doubles(int64_t rows) {
+    return (size_t)pca_tiles(rows) * (kPcaSumWidth + kPcaTri) + kPcaResult;
+}
+// pass 1: per-tile column sums and finite-row count, added in tile order; result[0] = n,
+// result[1..35] = mean (0 when n == 0)
+hipError_t launch_pca_sums(hipStream_t s, const double* betti, int64_t rows, double* workspace);
+// pass 2: per-tile scatter of the finite rows centred on result[1..35], added in tile order into
+// result[36..665]
+hipError_t launch_pca_scatter(hipStream_t s, const double* betti, int64_t rows, double* workspace);
+
 }  // namespace dgn

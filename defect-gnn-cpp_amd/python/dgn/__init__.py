@@ -3,8 +3,8 @@
 The product is the C ABI + HIP kernels; this module is plumbing (ctypes). It never falls back
 to a CPU implementation: without a GPU, every compute call raises DgnError(DGN_ERR_NODEVICE).
 """
-from .abi import (DGN_F32, DGN_F64, DGN_NONE, Batch, Context, DgnError, GraphParams, lib, lib_path,
-                  synth_batch)
+from .abi import (DGN_F32, DGN_F64, DGN_NONE, PCA_TILE_ROWS, Batch, Context, DgnError, GraphParams, PcaMoments, lib,
+                  lib_path, pca_merge, pca_solve, synth_batch)
 
-__all__ = ["DGN_F32", "DGN_F64", "DGN_NONE", "Batch", "Context", "DgnError", "GraphParams", "lib",
-           "lib_path", "synth_batch"]
+__all__ = ["DGN_F32", "DGN_F64", "DGN_NONE", "PCA_TILE_ROWS", "Batch", "Context", "DgnError", "GraphParams",
+           "PcaMoments", "lib", "lib_path", "pca_merge", "pca_solve", "synth_batch"]

@@ -24,10 +24,15 @@ EXPORTS = [
     "dgn_host_persistence_lower", "dgn_host_rbf", "dgn_debug_betti_clouds", "dgn_dev_node_features",
     "dgn_dev_edge_arrays", "dgn_host_edge_arrays", "dgn_edge_arrays_free", "dgn_dev_graph_betti",
     "dgn_synth_atoms_per_structure", "dgn_synth_batch", "dgn_ctx_set_debug", "dgn_debug_retry_count",
-    "dgn_debug_host_syncs", "dgn_debug_check_wide_layouts",
+    "dgn_debug_host_syncs", "dgn_debug_check_wide_layouts", "dgn_pca_moments_init", "dgn_dev_pca_accumulate",
+    "dgn_host_pca_accumulate", "dgn_pca_moments_merge", "dgn_pca_solve",
 ]
 DEBUG_FORCE_RETRY, DEBUG_WIDE_WAVES, DEBUG_WIDE_C16, DEBUG_WIDE_CAP, DEBUG_BIG_LOG2, DEBUG_EMIT_CHUNK = 1, 2, 3, 4, 6, 7
-DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE = 8, 9, 10
+DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE, DEBUG_PCA_CHUNK = 8, 9, 10, 11
+BETTI_DIM = 35  # DGN_BETTI_DIM
+# rows per tile of the PCA moment kernels: mirrors kPcaTileRows (csrc/dgn_internal.hpp); the tile, and
+# so the summation order of dgn_dev_pca_accumulate, does not depend on the device
+PCA_TILE_ROWS = 1024
 
 
 class DgnError(RuntimeError):
@@ -66,6 +71,41 @@ class BettiParams(C.Structure):
 class EdgeArrays(C.Structure):
     _fields_ = [("num_edges", C.c_int64), ("sources", C.POINTER(C.c_int32)), ("targets", C.POINTER(C.c_int32)),
                 ("distances", C.POINTER(C.c_float)), ("displacements", C.POINTER(C.c_float))]
+
+
+class PcaMoments(C.Structure):
+    """dgn_pca_moments: count, skipped (non-finite) rows, mean [35], centred scatter [35][35]."""
+    _fields_ = [("n", C.c_int64), ("skipped", C.c_int64), ("mean", C.c_double * BETTI_DIM),
+                ("m2", C.c_double * (BETTI_DIM * BETTI_DIM))]
+
+    @classmethod
+    def from_arrays(cls, n, mean, m2, skipped=0):
+        m = cls()
+        m.n, m.skipped = int(n), int(skipped)
+        m.mean[:] = np.asarray(mean, np.float64).reshape(BETTI_DIM).tolist()
+        m.m2[:] = np.asarray(m2, np.float64).reshape(BETTI_DIM * BETTI_DIM).tolist()
+        return m
+
+    def mean_array(self):
+        return np.array(self.mean[:], np.float64)
+
+    def m2_array(self):
+        return np.array(self.m2[:], np.float64).reshape(BETTI_DIM, BETTI_DIM)
+
+    def copy(self):
+        m = PcaMoments()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(PcaMoments))
+        return m
+
+    def tobytes(self):
+        return bytes(memoryview(self))
+
+    def __reduce__(self):  # pickled by torch.distributed's object collectives
+        return (_moments_from_bytes, (self.tobytes(),))
+
+
+def _moments_from_bytes(raw):
+    return PcaMoments.from_buffer_copy(raw)
 
 
 class KernelTime(C.Structure):
@@ -137,6 +177,12 @@ def lib():
         L.dgn_edge_arrays_free.restype = None
     if hasattr(L, "dgn_debug_betti_clouds"):  # absent from older A/B builds
         L.dgn_debug_betti_clouds.argtypes = [vp, vp, dbl, i64, i64, i32, vp, vp, vp]
+    L.dgn_pca_moments_init.argtypes = [C.POINTER(PcaMoments)]
+    L.dgn_pca_moments_init.restype = None
+    L.dgn_dev_pca_accumulate.argtypes = [vp, vp, i64, C.POINTER(PcaMoments)]
+    L.dgn_host_pca_accumulate.argtypes = [vp, vp, i64, C.POINTER(PcaMoments)]
+    L.dgn_pca_moments_merge.argtypes = [C.POINTER(PcaMoments), C.POINTER(PcaMoments)]
+    L.dgn_pca_solve.argtypes = [C.POINTER(PcaMoments), i32, vp, vp, vp]
     L.dgn_synth_atoms_per_structure.restype = i64
     L.dgn_synth_atoms_per_structure.argtypes = [C.c_int, C.c_int]
     L.dgn_synth_batch.argtypes = [C.c_int, C.c_int, i64, i64, vp, vp, vp, vp]
@@ -191,6 +237,28 @@ def graph_params(r_cutoff=10.0, max_neighbors=20, epsilon=1e-10, rbf_cutoff=10.0
     return p
 
 
+def pca_merge(a: PcaMoments, b: PcaMoments) -> PcaMoments:
+    """dgn_pca_moments_merge of b into a copy of a (host only, no context)."""
+    out = a.copy()
+    st = lib().dgn_pca_moments_merge(C.byref(out), C.byref(b))
+    if st:
+        raise DgnError(st, "dgn_pca_moments_merge")
+    return out
+
+
+def pca_solve(m: PcaMoments, k: int):
+    """dgn_pca_solve (host only, no context): (mean [35], components [35, k] row-major as
+    dev_node_features takes them, explained variance ratio [k])."""
+    k = int(k)
+    mean = np.zeros(BETTI_DIM)
+    comp = np.zeros((BETTI_DIM, max(k, 0)))
+    ratio = np.zeros(max(k, 0))
+    st = lib().dgn_pca_solve(C.byref(m), k, _ptr(mean), _ptr(comp), _ptr(ratio))
+    if st:
+        raise DgnError(st, "dgn_pca_solve")
+    return mean, comp, ratio
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.h = C.c_void_p()
@@ -219,8 +287,8 @@ class Context:
 
     def set_debug(self, knob: int, value: int):
         """Debug / A-B knob (DEBUG_FORCE_RETRY, DEBUG_WIDE_WAVES, DEBUG_WIDE_C16, DEBUG_WIDE_CAP,
-        DEBUG_BIG_LOG2, DEBUG_EMIT_CHUNK, DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE); tests and
-        tools only."""
+        DEBUG_BIG_LOG2, DEBUG_EMIT_CHUNK, DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE,
+        DEBUG_PCA_CHUNK); tests and tools only."""
         self._check(lib().dgn_ctx_set_debug(self.h, knob, value), "set_debug")
 
     def retry_count(self) -> int:
@@ -310,6 +378,26 @@ class Context:
         k = 0 if betti is None else int(pca_components.shape[1])
         self._check(lib().dgn_dev_node_features(self.h, C.byref(b), _ptr(embed), S, D, _ptr(betti), _ptr(pca_mean),
                                                 _ptr(pca_components), k, _ptr(out)), "dgn_dev_node_features")
+
+    def dev_pca_accumulate(self, feat, moments: PcaMoments | None = None) -> PcaMoments:
+        """Moments of a device tensor [rows][35] f64 (contiguous) merged into `moments` (a fresh
+        PcaMoments when None), which is returned. Waits for the stream once."""
+        m = PcaMoments() if moments is None else moments
+        if feat.dim() != 2 or feat.shape[1] != BETTI_DIM or not feat.is_contiguous() or feat.element_size() != 8:
+            raise ValueError("dev_pca_accumulate: feat must be a contiguous [rows][35] f64 tensor")
+        self._check(lib().dgn_dev_pca_accumulate(self.h, _ptr(feat), int(feat.shape[0]), C.byref(m)),
+                    "dgn_dev_pca_accumulate")
+        return m
+
+    def host_pca_accumulate(self, feat, moments: PcaMoments | None = None) -> PcaMoments:
+        """The same from a host array [rows][35], staged through the context in bounded chunks."""
+        m = PcaMoments() if moments is None else moments
+        f = np.ascontiguousarray(feat, dtype=np.float64)
+        if f.ndim != 2 or f.shape[1] != BETTI_DIM:
+            raise ValueError("host_pca_accumulate: feat must be [rows][35]")
+        self._check(lib().dgn_host_pca_accumulate(self.h, _ptr(f), int(f.shape[0]), C.byref(m)),
+                    "dgn_host_pca_accumulate")
+        return m
 
     def debug_betti_clouds(self, batch: dict, r_cutoff: float, atom_first: int, count: int, max_points: int):
         """Diagnostics: the Betti pass's local complexes of atoms [atom_first, atom_first + count):

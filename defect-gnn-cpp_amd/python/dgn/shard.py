@@ -88,3 +88,18 @@ def gather_csr(local: dict, dst: int = 0, group=None):
     objs = [None] * world if dist.get_rank(group) == dst else None
     dist.gather_object({k: np.asarray(v) for k, v in local.items()}, objs, dst=dst, group=group)
     return merge_csr(objs) if objs is not None else None
+
+
+def allreduce_pca_moments(local, group=None):
+    """One PCA model for every rank: gather each rank's PcaMoments (about 10 KB, as an object; no
+    tensor collective) and merge them in rank order on every rank, so that all ranks hold
+    bit-identical moments for dgn.pca_solve."""
+    import torch.distributed as dist
+
+    from . import abi
+    objs = [None] * dist.get_world_size(group)
+    dist.all_gather_object(objs, local, group=group)
+    out = abi.PcaMoments()
+    for m in objs:
+        out = abi.pca_merge(out, m)
+    return out

@@ -75,7 +75,9 @@ int dgn_ctx_synchronize(dgn_ctx* ctx);
  *                        takes at most this many clouds per chunk (its chunk loop on small inputs);
  * DGN_DEBUG_WALK_SLICE   > 0: a slice of the u16-coded wide list holds at most this many complexes (the
  *                        multi-slice loop, its second stream and buffer pair on small inputs); 0 = the
- *                        byte budgets' size. */
+ *                        byte budgets' size;
+ * DGN_DEBUG_PCA_CHUNK    > 0: dgn_host_pca_accumulate stages at most this many rows per chunk (its
+ *                        chunk loop on small inputs); 0 = the natural 262,144. */
 enum {
     DGN_DEBUG_FORCE_RETRY = 1,
     DGN_DEBUG_WIDE_WAVES = 2,
@@ -86,7 +88,8 @@ enum {
     DGN_DEBUG_EMIT_CHUNK = 7,
     DGN_DEBUG_WIDE_WALK = 8,
     DGN_DEBUG_SPLIT_CHUNK = 9,
-    DGN_DEBUG_WALK_SLICE = 10
+    DGN_DEBUG_WALK_SLICE = 10,
+    DGN_DEBUG_PCA_CHUNK = 11
 };
 int dgn_ctx_set_debug(dgn_ctx* ctx, int knob, int value);
 /* Diagnostics: complexes the capacity-retry launches reduced since the last call (synchronizes). */
@@ -234,6 +237,49 @@ int dgn_dev_graph_betti(dgn_ctx* ctx, const dgn_batch* batch, const dgn_graph_pa
 int dgn_dev_node_features(dgn_ctx* ctx, const dgn_batch* batch, const double* embed, int32_t num_keys, int32_t D,
                           const double* betti, const double* pca_mean, const double* pca_components, int32_t k,
                           double* out);
+
+/* ---- PCA fit from streaming, mergeable moments (PCA::fit) -----------
+ * Replaces the data pass of topology::PCA::fit (src/topology/pca.cpp:15-34: the column means, the
+ * centred matrix and its thin SVD) for Betti blocks that already lie in HBM. A block is reduced to
+ * count, mean and centred scatter; moments of further batches are accumulated into the same struct
+ * and moments of other shards or ranks are merged in (about 10 KB each); dgn_pca_solve then takes
+ * the eigenpairs of the 35 x 35 covariance on the host: the right singular vectors and
+ * s^2 / (N - 1) of pca.cpp:23-34. The output feeds dgn_dev_node_features as it stands.
+ * A row with any non-finite value (dgn_dev_betti writes NaN rows for failed atoms) is left out of
+ * count, mean and scatter alike and is counted in `skipped`. */
+enum { DGN_BETTI_DIM = 35 };
+typedef struct {
+    int64_t n;        /* rows accumulated                                             */
+    int64_t skipped;  /* rows left out because a value was not finite (failed atoms)  */
+    double mean[35];
+    double m2[35 * 35]; /* sum over rows of (x-mean)(x-mean)^T, symmetric, row-major    */
+} dgn_pca_moments;
+
+/* n = 0, skipped = 0, mean and m2 zero. */
+void dgn_pca_moments_init(dgn_pca_moments* m);
+/* betti_dev: [rows][35] f64 row-major in HBM, as dgn_dev_betti writes it; m: a host struct. Two passes
+ * over the block on the context's stream (column sums and finite-row count, then the scatter of the
+ * rows centred on that mean: pca.cpp:20-21), each per fixed-size row tile with the tiles' partials
+ * added in a fixed order, so two calls on the same data give bit-identical moments on any device.
+ * The call's own moments are read back (the call's one synchronization) and merged into *m as
+ * dgn_pca_moments_merge does. rows == 0: DGN_OK, *m untouched. */
+int dgn_dev_pca_accumulate(dgn_ctx* ctx, const double* betti_dev, int64_t rows, dgn_pca_moments* m);
+/* The same from a host matrix [rows][35] f64 row-major, staged through a context workspace in
+ * chunks of at most 262,144 rows (DGN_DEBUG_PCA_CHUNK caps the chunk), one dgn_dev_pca_accumulate
+ * per chunk: a 10^7-row matrix needs no 10^7-row device buffer. */
+int dgn_host_pca_accumulate(dgn_ctx* ctx, const double* betti_host, int64_t rows, dgn_pca_moments* m);
+/* Host only, no context. Pairwise update: n = na + nb, d = mean_b - mean_a, mean = mean_a + d nb / n,
+ * m2 = m2_a + m2_b + d d^T na nb / n; skipped counts add. Either side may have n == 0 (the other
+ * side's mean and m2 are then taken bit for bit). DGN_ERR_ARG: null or aliased pointers, negative
+ * counts. */
+int dgn_pca_moments_merge(dgn_pca_moments* into, const dgn_pca_moments* other);
+/* Host only, no context. Eigenpairs of m2 / (n - 1) (pca.cpp:23-34), eigenvalues descending, ties in
+ * index order; each component's largest-magnitude coefficient is positive (the facade's sign rule,
+ * cpp/include/topology/pca.hpp); explained_ratio[c] = lambda_c / sum of all 35 lambda, negative
+ * eigenvalues clamped to 0 (pca.cpp:31-33). mean [35], components [35][k] row-major (what
+ * dgn_dev_node_features takes), explained_ratio [k]; components and explained_ratio may be NULL when
+ * k == 0. DGN_ERR_ARG: k outside [0, 35], or n < 2 (no variance to explain). */
+int dgn_pca_solve(const dgn_pca_moments* m, int32_t k, double* mean, double* components, double* explained_ratio);
 
 /* ---- flat float32 edge arrays (WasmAPI graph accessors) ------------------
  * Replaces WasmAPI::num_edges / get_edge_sources / get_edge_targets / get_edge_distances /
