@@ -24,13 +24,19 @@
 //     minimum spanning forest in Ripser's order (ripser.cpp:725-762);
 //   * dim 1 and dim 2: cohomology with clearing. One lane per column finds its pivot (F-minimal
 //     cofacet) and settles apparent pairs (sigma youngest facet of tau, tau oldest cofacet of
-//     sigma). The wave then walks the remaining columns in Ripser's column order. A column is
-//     carried as its V list (the set of column simplices summed into it, Ripser's reduction
-//     matrix) with a membership bitmap in LDS; its pivot is recomputed lane-parallel as the
-//     F-minimal cofacet of odd multiplicity over the coboundaries of V (no sorting, no merging).
-//     Owners are looked up in a pivot table (serially resolved columns) or re-derived on the fly
-//     (apparent pairs). The persistence pairing of a total order is unique, so the emitted
-//     (birth, death) multiset equals the lock-free Ripser's (death > birth only; essential
+//     sigma). The remaining columns (up to 128: registers) are put in Ripser's column order, one
+//     per lane, each with its unreduced pivot; that register is at once the pivot table. The
+//     wave walks, in that order, only the columns that can need an addition -- the unreduced
+//     pivot has an apparent owner, or an earlier column holds (or ends up with) the same pivot --
+//     every other column keeps its unreduced pivot. A walked column is carried as its V list
+//     (the set of column simplices summed into it, Ripser's reduction matrix) in registers; its
+//     pivot is recomputed lane-parallel as the F-minimal cofacet of odd multiplicity over the
+//     coboundaries of V (no sorting, no merging). Owners are looked up among the lower ranks'
+//     pivots or re-derived on the fly (apparent pairs). Pairs, counts and clearing marks are
+//     written lane-parallel after the walk, in column order. More than 128 columns: every
+//     column is walked, from scratch tables.
+//     The persistence pairing of a total order is unique, so the emitted (birth, death) multiset
+//     equals the lock-free Ripser's (death > birth only; essential
 //     dim>=1 classes are not emitted, ripser.cpp:1209-1225).
 //   * persistent grid, chunked dynamic dequeue; per-wave global scratch for reduced columns
 //     and pair lists.
@@ -334,8 +340,9 @@ struct Complex {
         return dim == 1 ? ekey((cp >> 8) & 255, cp & 255) : tkey((cp >> 16) & 255, (cp >> 8) & 255, cp & 255);
     }
 
-    // ---- serially resolved pivot table: entries 0..127 in registers (lane t holds entries t
-    // and t + 64: pivot key and V-list descriptor), the rest in scratch
+    // ---- reduce_spilled's pivot table, in walk order: entries 0..127 in registers (lane t holds
+    // entries t and t + 64: pivot key and V-list descriptor), the rest in scratch. reduce_serial
+    // keeps only the V-list descriptors here (pm0 / pm1, by rank); its pivots are the records' T
     uint64_t pk0 = 0, pk1 = 0;
     uint32_t pm0 = 0, pm1 = 0;
 
@@ -542,116 +549,67 @@ struct Complex {
         __syncthreads();
     }
 
-    // Walk the non-apparent columns in Ripser's order (whole wave). na_* (scratch) hold each
-    // column's key and its unreduced pivot. Up to 128 records live in registers (lane t:
-    // records t and t + 64) with their rank in column order and the apparent owner of their
-    // initial pivot, all computed lane-parallel; larger sets are rank-sorted into scratch.
-    __device__ void reduce_serial(int dim, int nna) {
+    // V ^= V(owner) (whole wave, uniform arguments): the apparent owner `app` (V = {app}), else the
+    // resolved column with V-list descriptor m; false on V-list overflow
+    __device__ __forceinline__ bool add_owner(int dim, uint32_t app, uint32_t m, int& v) {
+        // an apparent owner precedes this column in Ripser's order (key greater): guaranteed (an
+        // apparent pair's column is the F-max facet of its pivot); checking it cost 2.4 % of the
+        // Betti pass, and the parity tests compare every pair with the oracle
+        if (app != kNone) return v_toggle(dim, app, v);
+        if (m & kLazyBit) return v_toggle(dim, m & ~kLazyBit, v);
+        const int lane = lane_id();
+        const uint32_t* gvstore = sp<uint32_t>(ScratchLayout::vstore);
+        const int off = (int)uni(m >> 9), len = (int)uni(m & 511);
+        bool ok = true;
+        // owner's V list: one lane-parallel load per 64 entries, then readlanes
+        for (int t0 = 0; t0 < len && ok; t0 += kWave) {
+            const int t = t0 + lane;
+            uint32_t w = 0;
+            if (t < len) w = at(gvstore, off + t);
+            const int cnt = len - t0 < kWave ? len - t0 : kWave;
+            for (int u = 0; u < cnt && ok; ++u) ok = v_toggle(dim, rl(w, u), v);
+        }
+        return ok;
+    }
+
+    // More than 128 non-apparent columns (rare: dense clouds; cold): walk every column in Ripser's
+    // order (whole wave). The records are rank-sorted into scratch (sna_*), the pivot table holds
+    // the resolved columns in walk order (find_pivot / piv_meta / piv_push: the first 128 in
+    // registers, the rest in scratch), and each column emits its pair and clearing mark itself.
+    __device__ void reduce_spilled(int dim, int nna) {
         const int lane = lane_id();
         if (nna > kNACap) { err |= kBErrNA; return; }
         const uint64_t* gk = sp<uint64_t>(ScratchLayout::na_key);
         const uint64_t* gt = sp<uint64_t>(ScratchLayout::na_tau);
-        const bool regs = nna <= 2 * kWave;
-        uint64_t rk0 = 0, rk1 = 0, rt0 = 0, rt1 = 0;
-        int rr0 = -1, rr1 = -1;
-        uint32_t ra0 = kNone, ra1 = kNone;
         uint64_t* sk = sp<uint64_t>(ScratchLayout::sna_key);
         uint64_t* st = sp<uint64_t>(ScratchLayout::sna_tau);
-        if (regs) {
-            if (lane < nna) { rk0 = at(gk, lane); rt0 = at(gt, lane); }
-            if (lane + kWave < nna) { rk1 = at(gk, lane + kWave); rt1 = at(gt, lane + kWave); }
-            // rank by column key DESCENDING (Ripser processes columns in decreasing F-order)
-            int r0 = 0, r1 = 0;
-            const int n0 = nna < kWave ? nna : kWave;
-            for (int u = 0; u < n0; ++u) {
-                const uint64_t ku = rl64(rk0, u);
-                r0 += ku > rk0;
-                r1 += ku > rk1;
-            }
-            for (int u = kWave; u < nna; ++u) {
-                const uint64_t ku = rl64(rk1, u - kWave);
-                r0 += ku > rk0;
-                r1 += ku > rk1;
-            }
-            rr0 = lane < nna ? r0 : -1;
-            rr1 = lane + kWave < nna ? r1 : -1;
-            // apparent owners of the initial pivots (global loads overlap across lanes)
-            if (lane < nna) ra0 = apparent_owner_lane(dim, rt0);
-            if (lane + kWave < nna) ra1 = apparent_owner_lane(dim, rt1);
-        } else {
-            for (int i = lane; i < nna; i += kWave) {
-                const uint64_t v = gk[i];
-                int rank = 0;
-                for (int u = 0; u < nna; ++u) rank += gk[u] > v;
-                sk[rank] = v;
-                st[rank] = gt[i];
-            }
-            __syncthreads();
+        // rank by column key DESCENDING (Ripser processes columns in decreasing F-order)
+        for (int i = lane; i < nna; i += kWave) {
+            const uint64_t v = gk[i];
+            int rank = 0;
+            for (int u = 0; u < nna; ++u) rank += gk[u] > v;
+            sk[rank] = v;
+            st[rank] = gt[i];
         }
+        __syncthreads();
         uint32_t* gvstore = sp<uint32_t>(ScratchLayout::vstore);
         int npiv = 0, vused = 0;
         for (int ci = 0; ci < nna; ++ci) {
-            uint64_t colkey, tau;
-            uint32_t app0 = kNone;
-            bool have_app = false;
-            if (regs) {
-                uint64_t bal = ballot(rr0 == ci);
-                if (bal) {
-                    const int l = __ffsll((unsigned long long)bal) - 1;
-                    colkey = rl64(rk0, l);
-                    tau = rl64(rt0, l);
-                    app0 = rl(ra0, l);
-                } else {
-                    bal = ballot(rr1 == ci);
-                    const int l = __ffsll((unsigned long long)bal) - 1;
-                    colkey = rl64(rk1, l);
-                    tau = rl64(rt1, l);
-                    app0 = rl(ra1, l);
-                }
-                have_app = true;
-            } else {
-                colkey = uni64(sk[ci]);
-                tau = uni64(st[ci]);
-            }
             // the walk's state is wave-uniform; readfirstlane says so to the compiler, whose
             // divergence analysis otherwise lets one vector-held value turn every branch of the
             // walk into exec-masked code
-            colkey = uni64(colkey);
-            tau = uni64(tau);
+            const uint64_t colkey = uni64(sk[ci]);
+            uint64_t tau = uni64(st[ci]);
             const uint32_t cp = key_packed(colkey);
             const uint32_t birth = key_code(colkey);
             int owner = (int)uni((uint32_t)find_pivot(npiv, tau));
-            uint32_t app = uni(owner >= 0 ? kNone : (have_app ? app0 : apparent_owner_wave(dim, tau)));
+            uint32_t app = uni(owner >= 0 ? kNone : apparent_owner_wave(dim, tau));
             int v = 0;  // 0 = lazy: V == {this column}
             if (owner >= 0 || app != kNone) {
                 v_toggle(dim, cp, v);
                 int guard = 0;
                 while (true) {
-                    // V ^= V(owner)
-                    bool ok = true;
-                    if (app != kNone) {
-                        // an apparent owner precedes this column in Ripser's order (key greater):
-                        // guaranteed (an apparent pair's column is the F-max facet of its pivot);
-                        // checking it cost 2.4 % of the Betti pass, and the parity tests compare
-                        // every pair with the oracle
-                        ok = v_toggle(dim, app, v);
-                    } else {
-                        const uint32_t m = piv_meta(owner);
-                        if (m & kLazyBit) {
-                            ok = v_toggle(dim, m & ~kLazyBit, v);
-                        } else {
-                            const int off = (int)uni(m >> 9), len = (int)uni(m & 511);
-                            // owner's V list: one lane-parallel load per 64 entries, then readlanes
-                            for (int t0 = 0; t0 < len && ok; t0 += kWave) {
-                                const int t = t0 + lane;
-                                uint32_t w = 0;
-                                if (t < len) w = at(gvstore, off + t);
-                                const int cnt = len - t0 < kWave ? len - t0 : kWave;
-                                for (int u = 0; u < cnt && ok; ++u) ok = v_toggle(dim, rl(w, u), v);
-                            }
-                        }
-                    }
-                    if (!ok) { err |= kBErrWorkCol; return; }
+                    if (!add_owner(dim, app, app != kNone ? 0u : piv_meta(owner), v)) { err |= kBErrWorkCol; return; }
                     tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);
                     if (tau == kInf) break;  // zero column: essential class, not emitted
                     owner = (int)uni((uint32_t)find_pivot(npiv, tau));
@@ -692,6 +650,217 @@ struct Complex {
             npiv = (int)uni((uint32_t)(npiv + 1));
             wave_lds_sync();
         }
+    }
+
+    // pivot lookup of the rank-ordered walk: the rank below `ci` whose current pivot is tau, or -1.
+    // t0 / t1 hold the pivots of ranks lane and lane + 64 (kInf: zero column, or no record).
+    __device__ __forceinline__ static int find_rank(uint64_t t0, uint64_t t1, int ci, uint64_t tau) {
+        uint64_t bal = ballot(t0 == tau) & lanes_below(ci);
+        if (bal) return __ffsll((unsigned long long)bal) - 1;
+        if (ci > kWave) {
+            bal = ballot(t1 == tau) & lanes_below(ci - kWave);
+            if (bal) return kWave + __ffsll((unsigned long long)bal) - 1;
+        }
+        return -1;
+    }
+
+    // per-complex census of the rank-ordered walk (BettiLaunch::col_stats), wave-uniform: columns
+    // (bits 0-9), columns walked (10-19), columns in the initial visit mask (20-29), reductions
+    // that took reduce_spilled (30-31)
+    uint32_t cstat = 0;
+
+    // The non-apparent columns of one dimension (whole wave). na_* (scratch) hold each column's
+    // key K and its unreduced pivot T. Up to 128 columns (more: reduce_spilled) live in registers
+    // in Ripser's column order: lane r holds the records of ranks r and r + 64, and T is at once
+    // the pivot table -- lane r's T is the current pivot of the column at rank r (kInf for a zero
+    // column and for lanes without a record), final once the walk has passed r. Only the columns
+    // that can need an addition are walked (the wave-uniform mask N): those whose initial pivot
+    // has an apparent owner or is shared with a lower rank, and those whose initial pivot a walked
+    // column finalises with (promoted then). Every other column keeps T as its pivot with
+    // V = {column}. Pairs, counts and clearing marks come from K and T lane-parallel after the
+    // walk, in rank order (the emission order of a walk over every column). visit_all: N = all
+    // columns (tests).
+    __device__ void reduce_serial(int dim, int nna, bool visit_all) {
+        if (nna > 2 * kWave) {
+            reduce_spilled(dim, nna);
+            cstat += 1u << 30;
+            return;
+        }
+        if (nna == 0) return;
+        const int lane = lane_id();
+        // rank by column key DESCENDING (Ripser processes columns in decreasing F-order) and note
+        // whether a lower rank (greater key) starts from the same pivot; then each record moves to
+        // the lane of its rank (the keys are distinct, so the ranks are a permutation of
+        // 0..nna-1), the shared-pivot flag riding in T's top bit (a key's high word is a u16 code)
+        uint64_t k0 = 0, k1 = 0, t0 = kInf, t1 = kInf;
+        uint64_t nv0, nv1;  // N: ranks 0..63, 64..127
+        constexpr uint64_t kShared = 1ull << 63;
+        const uint64_t* gk = sp<uint64_t>(ScratchLayout::na_key);
+        const uint64_t* gt = sp<uint64_t>(ScratchLayout::na_tau);
+        if (nna <= kWave) {
+            // one register set: the ranks (lanes without a record keep their own lane) are a
+            // permutation of the 64 lanes, so the move is one ds_permute per word (no memory)
+            uint64_t uk0 = 0, ut0 = kInf;
+            if (lane < nna) { uk0 = at(gk, lane); ut0 = at(gt, lane); }
+            int r0 = 0;
+            bool sh0 = false;
+            for (int u = 0; u < nna; ++u) {
+                const uint64_t ku = rl64(uk0, u), tu = rl64(ut0, u);
+                const bool g0 = ku > uk0;
+                r0 += g0;
+                sh0 |= g0 && tu == ut0;
+            }
+            const bool have = lane < nna;
+            dgn_check(!have || r0 < nna);
+            const int dst = (have ? r0 : lane) << 2;
+            const uint32_t thi = (uint32_t)(ut0 >> 32) | (have && sh0 ? (uint32_t)(kShared >> 32) : 0u);
+            const uint32_t pkl = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)uk0);
+            const uint32_t pkh = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)(uk0 >> 32));
+            const uint32_t ptl = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)ut0);
+            const uint32_t pth = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)thi);
+            k0 = ((uint64_t)pkh << 32) | pkl;
+            t0 = have ? (((uint64_t)pth << 32) | ptl) & ~kShared : kInf;
+            nv0 = ballot(have && (pth >> 31) != 0);
+            nv1 = 0;
+        } else {
+            uint64_t* sk = sp<uint64_t>(ScratchLayout::sna_key);
+            uint64_t* st = sp<uint64_t>(ScratchLayout::sna_tau);
+            // two register sets (65..128 columns): lane t lists records t and t + 64
+            uint64_t uk0 = at(gk, lane), ut0 = at(gt, lane), uk1 = 0, ut1 = kInf;
+            if (lane + kWave < nna) { uk1 = at(gk, lane + kWave); ut1 = at(gt, lane + kWave); }
+            int r0 = 0, r1 = 0;
+            bool sh0 = false, sh1 = false;
+            for (int u = 0; u < kWave; ++u) {
+                const uint64_t ku = rl64(uk0, u), tu = rl64(ut0, u);
+                const bool g0 = ku > uk0, g1 = ku > uk1;
+                r0 += g0;
+                r1 += g1;
+                sh0 |= g0 && tu == ut0;
+                sh1 |= g1 && tu == ut1;
+            }
+            for (int u = kWave; u < nna; ++u) {
+                const uint64_t ku = rl64(uk1, u - kWave), tu = rl64(ut1, u - kWave);
+                const bool g0 = ku > uk0, g1 = ku > uk1;
+                r0 += g0;
+                r1 += g1;
+                sh0 |= g0 && tu == ut0;
+                sh1 |= g1 && tu == ut1;
+            }
+            // each record to the lane of its rank, through scratch (sna_*)
+            dgn_check(r0 < nna);
+            at(sk, r0) = uk0;
+            at(st, r0) = ut0 | (sh0 ? kShared : 0ull);
+            if (lane + kWave < nna) {
+                dgn_check(r1 < nna);
+                at(sk, r1) = uk1;
+                at(st, r1) = ut1 | (sh1 ? kShared : 0ull);
+            }
+            __syncthreads();  // the records (scratch) are read by other lanes
+            k0 = at(sk, lane);
+            t0 = at(st, lane);
+            const bool in0 = (t0 & kShared) != 0;
+            t0 &= ~kShared;
+            bool in1 = false;
+            if (lane + kWave < nna) {
+                k1 = at(sk, lane + kWave);
+                t1 = at(st, lane + kWave);
+                in1 = (t1 & kShared) != 0;
+                t1 &= ~kShared;
+            }
+            nv0 = ballot(in0);
+            nv1 = ballot(in1);
+        }
+        // apparent owners of the initial pivots (global loads overlap across lanes); every column
+        // starts lazy: V = {column}
+        uint32_t ra0 = kNone, ra1 = kNone;
+        if (lane < nna) ra0 = apparent_owner_lane(dim, t0);
+        if (lane + kWave < nna) ra1 = apparent_owner_lane(dim, t1);
+        pm0 = kLazyBit | key_packed(k0);
+        pm1 = kLazyBit | key_packed(k1);
+        nv0 |= ballot(ra0 != kNone);
+        nv1 |= ballot(ra1 != kNone);
+        if (visit_all) {
+            nv0 = lanes_below(nna);
+            nv1 = lanes_below(nna - kWave);
+        }
+        const int ninit = __popcll(nv0) + __popcll(nv1);
+        uint32_t* gvstore = sp<uint32_t>(ScratchLayout::vstore);
+        int vused = 0, walked = 0;
+        // every visit clears one rank of N and adds only higher ones: at most nna visits
+        for (; walked < nna; ++walked) {
+            // the lowest rank of N, branch-free on the register set (scalar selects; the record's
+            // set is picked per lane before one v_readlane per word)
+            const bool hi = nv0 == 0;
+            const uint64_t nv = hi ? nv1 : nv0;
+            if (nv == 0) break;
+            const int cl = __ffsll((unsigned long long)nv) - 1;  // the record's lane
+            nv0 = hi ? nv0 : (nv & (nv - 1));
+            nv1 = hi ? (nv & (nv - 1)) : nv1;
+            const int ci = cl + (hi ? kWave : 0);
+            // the walk's state is wave-uniform; readfirstlane says so to the compiler, whose
+            // divergence analysis otherwise lets one vector-held value turn every branch of the
+            // walk into exec-masked code
+            const uint32_t cp = uni(rl(hi ? key_packed(k1) : key_packed(k0), cl));
+            uint64_t tau = uni64(rl64(hi ? t1 : t0, cl));
+            const uint32_t app0 = rl(hi ? ra1 : ra0, cl);
+            int owner = (int)uni((uint32_t)find_rank(t0, t1, ci, tau));
+            uint32_t app = uni(owner >= 0 ? kNone : app0);
+            int v = 0;  // 0 = lazy: V == {this column}
+            if (owner >= 0 || app != kNone) {
+                v_toggle(dim, cp, v);
+                int guard = 0;
+                while (true) {
+                    // (owner -1 with an apparent owner: a harmless read of lane 63, unused)
+                    const uint32_t m = rl(owner < kWave ? pm0 : pm1, owner & (kWave - 1));
+                    if (!add_owner(dim, app, m, v)) { err |= kBErrWorkCol; return; }
+                    tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);
+                    if (tau == kInf) break;  // zero column: essential class, not emitted
+                    owner = (int)uni((uint32_t)find_rank(t0, t1, ci, tau));
+                    app = uni(owner >= 0 ? kNone : apparent_owner_wave(dim, tau));
+                    if (owner < 0 && app == kNone) break;  // tau is this column's pivot
+                    if (++guard > 100000) { err |= kBErrWorkCol; return; }
+                }
+            }
+            // ---- tau is the pivot of this column (kInf: zero column) ----
+            t0 = lane == ci ? tau : t0;
+            t1 = lane == ci - kWave ? tau : t1;
+            if (tau != kInf) {
+                // later columns that start from tau have an owner now
+                nv0 |= ballot(t0 == tau) & ~lanes_below(ci + 1);
+                nv1 |= ballot(t1 == tau) & ~lanes_below(ci + 1 - kWave);
+                if (v != 0) {
+                    if (vused + v > kVStoreCap || v > 511) { err |= kBErrR; return; }
+                    // v <= kVCap: one store per register set
+                    if (lane < v) at(gvstore, vused + lane) = vs0;
+                    if (lane + kWave < v) at(gvstore, vused + kWave + lane) = vs1;
+                    const uint32_t meta = ((uint32_t)vused << 9) | (uint32_t)v;
+                    pm0 = lane == ci ? meta : pm0;
+                    pm1 = lane == ci - kWave ? meta : pm1;
+                    vused = (int)uni((uint32_t)(vused + v));
+                }
+            }
+            wave_lds_sync();
+        }
+        // ---- pairs, counts and clearing marks of every column at once ----
+        // codes order as the distances (ripser.cpp:1240); rank order, set 0 then set 1
+        const uint32_t b0 = key_code(k0), b1 = key_code(k1), d0 = key_code(t0), d1 = key_code(t1);
+        const bool e0 = t0 != kInf && d0 > b0, e1 = t1 != kInf && d1 > b1;
+        const uint64_t eb0 = ballot(e0), eb1 = ballot(e1);
+        const int base = dim == 1 ? n_p1 : n_p2;
+        const int s0 = base + mask_prefix(eb0), s1 = base + __popcll(eb0) + mask_prefix(eb1);
+        if (e0 && s0 < kPairCap) at(pair_codes(dim), s0) = make_uint2(b0, d0);
+        if (e1 && s1 < kPairCap) at(pair_codes(dim), s1) = make_uint2(b1, d1);
+        const int np = (int)uni((uint32_t)(base + __popcll(eb0) + __popcll(eb1)));
+        if (dim == 1) {
+            n_p1 = np;
+            // clearing: the dim-2 pass skips every dim-1 pivot
+            const uint32_t p0 = key_packed(t0), p1 = key_packed(t1);
+            if (t0 != kInf) set_cleared_lane((p0 >> 16) & 255, (p0 >> 8) & 255, p0 & 255);
+            if (t1 != kInf) set_cleared_lane((p1 >> 16) & 255, (p1 >> 8) & 255, p1 & 255);
+        } else {
+            n_p2 = np;
+        }
+        cstat += (uint32_t)nna | ((uint32_t)walked << 10) | ((uint32_t)ninit << 20);
     }
 
     // ---- the phases of one complex (whole wave), in betti_kernel's order. Each takes the lane
@@ -1135,7 +1304,7 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
             uint32_t* defer = cx.template sp<uint32_t>(ScratchLayout::defer);
             if (dim_max >= 1) {
                 const int nna = cx.apparent_dim1(n_edges);
-                cx.reduce_serial(1, nna);
+                cx.reduce_serial(1, nna, bl.visit_all != 0);
                 __syncthreads();  // clearing marks (scratch stores) complete before the dim-2 pass
             }
             if (!(dim_max >= 2 && cx.err == 0) && n >= 3) {
@@ -1271,12 +1440,14 @@ __global__ __launch_bounds__(kWave, betti_waves_per_simd<NP>()) void betti_kerne
                     }
                 }
                 __syncthreads();
-                cx.reduce_serial(2, nna);
+                cx.reduce_serial(2, nna, bl.visit_all != 0);
                 wave_lds_sync();
             }
             __syncthreads();
             if (cx.n_p1 > kPairCap || cx.n_p2 > kPairCap) cx.err |= kBErrPairs;
             const uint32_t err = uni(cx.err);
+            if (bl.col_stats && lane < 4)  // census of the walks (tests, profiles): one atomic per complex
+                atomicAdd(bl.col_stats + lane, (unsigned long long)((cx.cstat >> (10 * lane)) & (lane < 3 ? 1023u : 3u)));
             if (err && bl.retry_list && (err & kBErrCapacity) == err) {
                 // workspace overflow: the capacity-retry launch (betti_wide_kernel, big layout)
                 // reduces this complex again and writes its outputs

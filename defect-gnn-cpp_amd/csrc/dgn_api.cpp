@@ -158,6 +158,9 @@ struct dgn_ctx {
     int dbg_big_log2 = 0;          // capacity-retry layout's first-level table size log2 (0 = natural 24)
     int dbg_emit_chunk = 0;        // tiles per launch of the large-row emit (0 = the byte budget's)
     int dbg_pca_chunk = 0;         // rows per staged chunk of dgn_host_pca_accumulate (0 = kPcaHostChunkRows)
+    bool dbg_visit_all = false;    // the narrow Betti walk visits every column
+    bool dbg_col_stats = false;    // the narrow Betti kernels add their column census to col_stats
+    DevBuf col_stats;              // [4] uint64 (BettiLaunch::col_stats), read and cleared by dgn_debug_column_stats
     DevBuf pca_work, pca_stage;    // PCA moments: tile partials + result; the host entry point's staged rows
     // host staging
     DevBuf h_lat, h_pos, h_spec, h_off;
@@ -558,6 +561,15 @@ int betti_prepare(dgn_ctx* c, const BettiJob& job, int64_t A, BettiPass& P) {
     bl.wide_queue = &sc->wide_queue;
     bl.retry_len = &sc->retry_len;  // retry_list: betti_impl
     bl.force_retry = c->dbg_force_retry ? 1 : 0;  // tests only (dgn_ctx_set_debug)
+    bl.visit_all = c->dbg_visit_all ? 1 : 0;
+    bl.col_stats = nullptr;
+    if (c->dbg_col_stats) {
+        if (!c->col_stats.p) {
+            HIP_TRY(c, c->col_stats.ensure(4 * sizeof(uint64_t)));
+            HIP_TRY(c, hipMemsetAsync(c->col_stats.p, 0, 4 * sizeof(uint64_t), c->stream));
+        }
+        bl.col_stats = c->col_stats.as<unsigned long long>();
+    }
     return DGN_OK;
 }
 
@@ -1159,6 +1171,8 @@ int dgn_ctx_set_debug(dgn_ctx* c, int knob, int value) {
         case DGN_DEBUG_BIG_LOG2: c->dbg_big_log2 = value > 0 && value < 24 ? value : 0; return DGN_OK;
         case DGN_DEBUG_EMIT_CHUNK: c->dbg_emit_chunk = value > 0 ? value : 0; return DGN_OK;
         case DGN_DEBUG_PCA_CHUNK: c->dbg_pca_chunk = value > 0 ? value : 0; return DGN_OK;
+        case DGN_DEBUG_NARROW_VISIT_ALL: c->dbg_visit_all = value != 0; return DGN_OK;
+        case DGN_DEBUG_COLUMN_STATS: c->dbg_col_stats = value != 0; return DGN_OK;
         default: return fail(c, DGN_ERR_ARG, "dgn_ctx_set_debug: unknown knob " + std::to_string(knob));
     }
 }
@@ -1178,6 +1192,21 @@ int dgn_debug_retry_count(dgn_ctx* c, int64_t* out) {
     HIP_TRY(c, hipMemsetAsync(c->bflags.as<uint32_t>() + kBFRetried, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(c, stream_sync(c));
     *out = c->host->pad;
+    return take_flags(c);
+}
+
+int dgn_debug_column_stats(dgn_ctx* c, int64_t out[4]) {
+    if (!c || !out) return DGN_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (!c->col_stats.p) return DGN_OK;
+    uint64_t raw[4];  // columns, walked, in the initial visit mask, reductions above 128 columns
+    HIP_TRY(c, hipMemcpyAsync(raw, c->col_stats.p, sizeof(raw), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->col_stats.p, 0, sizeof(raw), c->stream));
+    HIP_TRY(c, stream_sync(c));
+    out[0] = (int64_t)(raw[0] - raw[1]);
+    out[1] = (int64_t)raw[1];
+    out[2] = (int64_t)(raw[1] - raw[2]);
+    out[3] = (int64_t)raw[3];
     return take_flags(c);
 }
 

@@ -178,6 +178,10 @@ struct BettiLaunch {
     int32_t* retry_list;      // [num_atoms]
     uint32_t* retry_len;
     int32_t force_retry;      // tests (DGN_DEBUG_FORCE_RETRY): the host lists every complex for the retry launch
+    int32_t visit_all;        // tests (DGN_DEBUG_NARROW_VISIT_ALL): the narrow walk visits every column
+    // narrow kernels, or null: += per complex {columns, columns walked, columns in the initial visit
+    // mask, reductions of more than 128 columns} of the rank-ordered walk (dgn_debug_column_stats)
+    unsigned long long* col_stats;
     uint32_t* retried;        // capacity-retry launches: +1 per complex reduced (diagnostics counter), or null
     // complexes above kWideRegular points (the retry launch's BIG wide instantiation): per retry
     // slot r, rank codes of the packed lower triangle and the sorted f32 distances (betti_rank_codes)

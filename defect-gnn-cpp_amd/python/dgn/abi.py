@@ -25,10 +25,11 @@ EXPORTS = [
     "dgn_dev_edge_arrays", "dgn_host_edge_arrays", "dgn_edge_arrays_free", "dgn_dev_graph_betti",
     "dgn_synth_atoms_per_structure", "dgn_synth_batch", "dgn_ctx_set_debug", "dgn_debug_retry_count",
     "dgn_debug_host_syncs", "dgn_debug_check_wide_layouts", "dgn_pca_moments_init", "dgn_dev_pca_accumulate",
-    "dgn_host_pca_accumulate", "dgn_pca_moments_merge", "dgn_pca_solve",
+    "dgn_host_pca_accumulate", "dgn_pca_moments_merge", "dgn_pca_solve", "dgn_debug_column_stats",
 ]
 DEBUG_FORCE_RETRY, DEBUG_WIDE_WAVES, DEBUG_WIDE_C16, DEBUG_WIDE_CAP, DEBUG_BIG_LOG2, DEBUG_EMIT_CHUNK = 1, 2, 3, 4, 6, 7
 DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE, DEBUG_PCA_CHUNK = 8, 9, 10, 11
+DEBUG_NARROW_VISIT_ALL, DEBUG_COLUMN_STATS = 12, 13
 BETTI_DIM = 35  # DGN_BETTI_DIM
 # rows per tile of the PCA moment kernels: mirrors kPcaTileRows (csrc/dgn_internal.hpp); the tile, and
 # so the summation order of dgn_dev_pca_accumulate, does not depend on the device
@@ -143,6 +144,8 @@ def lib():
         L.dgn_ctx_set_debug.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "dgn_debug_retry_count"):
         L.dgn_debug_retry_count.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "dgn_debug_column_stats"):
+        L.dgn_debug_column_stats.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "dgn_debug_host_syncs"):
         L.dgn_debug_host_syncs.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "dgn_debug_check_wide_layouts"):
@@ -288,7 +291,7 @@ class Context:
     def set_debug(self, knob: int, value: int):
         """Debug / A-B knob (DEBUG_FORCE_RETRY, DEBUG_WIDE_WAVES, DEBUG_WIDE_C16, DEBUG_WIDE_CAP,
         DEBUG_BIG_LOG2, DEBUG_EMIT_CHUNK, DEBUG_WIDE_WALK, DEBUG_SPLIT_CHUNK, DEBUG_WALK_SLICE,
-        DEBUG_PCA_CHUNK); tests and tools only."""
+        DEBUG_PCA_CHUNK, DEBUG_NARROW_VISIT_ALL, DEBUG_COLUMN_STATS); tests and tools only."""
         self._check(lib().dgn_ctx_set_debug(self.h, knob, value), "set_debug")
 
     def retry_count(self) -> int:
@@ -296,6 +299,14 @@ class Context:
         n = C.c_int64()
         self._check(lib().dgn_debug_retry_count(self.h, C.byref(n)), "retry_count")
         return n.value
+
+    def column_stats(self) -> dict:
+        """Column census of the narrow Betti kernels since the last call, collected while
+        DEBUG_COLUMN_STATS is 1 (synchronizes): columns skipped, walked, promoted into the visit
+        set by an earlier column's final pivot, and reductions of more than 128 columns."""
+        v = (C.c_int64 * 4)()
+        self._check(lib().dgn_debug_column_stats(self.h, v), "column_stats")
+        return {"skipped": v[0], "walked": v[1], "promoted": v[2], "spilled": v[3]}
 
     def host_syncs(self) -> int:
         """Host waits on the context's stream since the last call (no synchronization itself)."""

@@ -77,7 +77,11 @@ int dgn_ctx_synchronize(dgn_ctx* ctx);
  *                        multi-slice loop, its second stream and buffer pair on small inputs); 0 = the
  *                        byte budgets' size;
  * DGN_DEBUG_PCA_CHUNK    > 0: dgn_host_pca_accumulate stages at most this many rows per chunk (its
- *                        chunk loop on small inputs); 0 = the natural 262,144. */
+ *                        chunk loop on small inputs); 0 = the natural 262,144;
+ * DGN_DEBUG_NARROW_VISIT_ALL  1 = the narrow Betti kernels (<= 64 points) walk every non-apparent
+ *                        column instead of only those that can need an addition (same outputs);
+ * DGN_DEBUG_COLUMN_STATS 1 = the narrow Betti kernels count their walks' columns for
+ *                        dgn_debug_column_stats (one atomic per complex); 0 = off (default). */
 enum {
     DGN_DEBUG_FORCE_RETRY = 1,
     DGN_DEBUG_WIDE_WAVES = 2,
@@ -89,11 +93,19 @@ enum {
     DGN_DEBUG_WIDE_WALK = 8,
     DGN_DEBUG_SPLIT_CHUNK = 9,
     DGN_DEBUG_WALK_SLICE = 10,
-    DGN_DEBUG_PCA_CHUNK = 11
+    DGN_DEBUG_PCA_CHUNK = 11,
+    DGN_DEBUG_NARROW_VISIT_ALL = 12,
+    DGN_DEBUG_COLUMN_STATS = 13
 };
 int dgn_ctx_set_debug(dgn_ctx* ctx, int knob, int value);
 /* Diagnostics: complexes the capacity-retry launches reduced since the last call (synchronizes). */
 int dgn_debug_retry_count(dgn_ctx* ctx, int64_t* count);
+/* Diagnostics (after DGN_DEBUG_COLUMN_STATS = 1): the narrow Betti kernels' column census since the
+ * last call, over both dimensions of every complex they reduced (synchronizes): stats[0] = columns
+ * the walk skipped (they keep their initial pivot), [1] = columns walked, [2] = walked columns
+ * that entered the visit set only when an earlier column finalised with their initial pivot,
+ * [3] = reductions of more than 128 columns (walked in full, not counted in [0..2]). */
+int dgn_debug_column_stats(dgn_ctx* ctx, int64_t stats[4]);
 /* Diagnostics: how many times the context's calls waited for its stream since the last call
  * (no synchronization itself; tests of the asynchronous device entry points). */
 int dgn_debug_host_syncs(dgn_ctx* ctx, int64_t* count);

@@ -11,14 +11,19 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.environ.get("ISA_CSRC") or os.path.join(ROOT, "defect-gnn-cpp_amd", "csrc")
+# anchors inside Complex::reduce_serial (searched from its definition on: reduce_spilled, before it,
+# shares some of these lines)
+START = "    __device__ void reduce_serial(int dim, int nna, bool visit_all) {\n"
 MARKS = [
-    ("        for (int ci = 0; ci < nna; ++ci) {\n", "COL_TOP", True),
-    ("            int owner = (int)uni((uint32_t)find_pivot(npiv, tau));\n", "AFTER_FIND", True),
+    ("        for (; walked < nna; ++walked) {\n", "COL_TOP", True),
+    ("            int owner = (int)uni((uint32_t)find_rank(t0, t1, ci, tau));\n", "AFTER_FIND", True),
     ("            int v = 0;  // 0 = lazy: V == {this column}\n", "AFTER_APP", True),
     ("                    tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);\n", "PIV", False),
     ("                    tau = uni64(v > 0 ? pivot_of_V(dim, v, tau) : kInf);\n", "AFTER_PIV", True),
-    ("            // ---- tau is the pivot of this column ----\n", "FINAL", True),
-    ("            npiv = (int)uni((uint32_t)(npiv + 1));\n            wave_lds_sync();\n", "FINAL_END", True),
+    ("            // ---- tau is the pivot of this column (kInf: zero column) ----\n", "FINAL", True),
+    ("            wave_lds_sync();\n        }\n        // ---- pairs, counts and clearing marks of every column at once ----\n",
+     "FINAL_END", True),
+    ("        cstat += (uint32_t)nna | ((uint32_t)walked << 10) | ((uint32_t)ninit << 20);\n", "EPILOGUE_END", True),
 ]
 
 
@@ -30,10 +35,13 @@ def main():
         shutil.copy(os.path.join(CSRC, f), out)
     p = os.path.join(out, "betti_kernels.hip")
     s = open(p).read()
+    base = s.index(START)
+    head, s = s[:base], s[base:]
     for anchor, name, after in MARKS:
         assert anchor in s, name
         m = f'asm volatile("; MARK_{name}");\n'
         s = s.replace(anchor, anchor + m if after else m + anchor, 1)
+    s = head + s
     open(p, "w").write(s)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
                     "-I" + out, "-I" + os.path.join(ROOT, "include"), "-mllvm", "-amdgpu-sched-strategy=iterative-minreg", "--save-temps", "-c", p, "-o",
